@@ -1,6 +1,6 @@
 """Benchmark: CAT-Seg dense inference, images/sec @ ViT-L/14 336², 150 classes, bs=8 per GPU.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5]
+  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 One step = the full eval forward of one batch of synthetic images already resident in HBM:
@@ -9,16 +9,22 @@ layers -> guided upsampler -> sigmoid logits bilinearly upsampled to the CLIP re
 (cat_seg_model.py:147-229).  Class embeddings of the dataset's prompts are encoded once on
 the GPU before timing (the predictor's eval cache, cat_seg_predictor.py:191-192).  With
 N > 1 each rank runs its own batch and the (B, T, 96, 96) logits are all-gathered over RCCL
-(weak scaling); after timing, rank 0 re-runs every rank's seeded batch and checks that the
-gathered logits equal its own, bit for bit (the multi-GPU parity gate).
+(weak scaling).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR also
+writes what the last timed step computed (the head logits and the probabilities, DIR/<name>.npy,
+fp32; an array over 16 MiB as a fixed seeded sample of its elements).  --full adds the legs that
+take runs of their own: the drop-in boundary leg, the per-kernel roofline pass, the CPU baseline
+and, with N > 1, the multi-GPU parity gate (after timing, rank 0 re-runs every rank's seeded batch
+and checks that the gathered logits equal its own, bit for bit).
 
 Configs: 3 = the headline (L/14@336, T=150, bs=8, bf16); 2 = B/16@384, T=150,
 bs=4, fp32 (exact-f32 MFMA); 4 = L/14@336, ade847 -> top-256, 4 images/GPU; 5 = sliding-window
 640², pc459, fp8 ViT GEMMs.
 
-Prints ONE JSON line (rank 0) with the metric, a roofline object for the dominant kernel
-(HIP-event timed per launch on the launch stream, algorithmic FLOPs from the launch shapes)
-and the CPU baseline (the oracle, rank 0 at N=1 only).
+Prints ONE JSON line (rank 0) with the metric and, with --full, a roofline object for the
+dominant kernel (HIP-event timed per launch on the launch stream, algorithmic FLOPs from the
+launch shapes) and the CPU baseline (the oracle, rank 0 at N=1 only).
 """
 from __future__ import annotations
 
@@ -75,6 +81,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (0 = the config's)")
     ap.add_argument("--classes", type=int, default=0, help="class count (0 = the config's)")
     ap.add_argument("--dtype", default="", choices=["", "bf16", "f32"], help="engine dtype ('' = the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: boundary, roofline, CPU baseline and "
+                         "(N > 1) the multi-GPU parity gate; the --no-* / --cpu-images switches trim them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (fp32)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph per step")
     ap.add_argument("--cpu-images", type=int, default=-1,
                     help="oracle sample size for cpu_baseline (-1 = the benched batch, 0 = skip)")
@@ -182,11 +193,13 @@ def main():
     gsize = 4 * arch.grid
     rows = 5 * B if cfg5 else B          # gathered logit planes per rank (config 5: 4 tiles + global per image)
 
+    final = [out]      # the step's last-stage output (the probabilities), for --dump-outputs
+
     def step():
         if cfg5:
             # crops + head + Fold merge -> 640² probabilities at the image size (sem_seg_postprocess is the
             # identity at 640²); the crops' logits (5 per image, 96²) are what N > 1 all-gathers
-            _, crop_logits = eng.sliding_logits(raw, sizes, return_crops=True)
+            final[0], crop_logits = eng.sliding_logits(raw, sizes, return_crops=True)
             return crop_logits
         logits = eng.head_logits(raw, sizes)
         ops.postprocess(logits, out, crop=(min(logits.shape[-2], R), min(logits.shape[-1], R)))
@@ -201,7 +214,7 @@ def main():
     stream = torch.cuda.Stream(device=dev)
     overlap = world > 1 and backend == "nccl"
     nbuf = 2 if world > 1 else 1
-    graphs, g_logits = [], []
+    graphs, g_logits, g_final = [], [], []
     gathered = ([torch.empty(world * rows, T, gsize, gsize, device=dev) for _ in range(nbuf)]
                 if world > 1 else None)
     works = [None] * nbuf
@@ -214,6 +227,7 @@ def main():
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=stream):
                     g_logits.append(step())
+                g_final.append(final[0])
                 graphs.append(g)
 
         def forward_once(i=0):
@@ -240,14 +254,19 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last_logits = None
         for i in range(args.steps):
-            run(args.warmup + i)
+            last_logits = run(args.warmup + i)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         last = (args.warmup + args.steps - 1) % nbuf
+        if args.dump_outputs and last_logits is not None:
+            # before anything below rewrites the step's buffers
+            dump_outputs(args.dump_outputs, "" if world == 1 else f"_rank{rank}",
+                         {"logits": last_logits, "probs": g_final[last] if graphs else final[0]})
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64)
             t = t.to(dev) if backend == "nccl" else t
@@ -256,7 +275,7 @@ def main():
         # multi-GPU parity gate: rank 0 recomputes every rank's seeded batch on its own GPU and
         # compares with that rank's slice of the last step's gathered logits, bit for bit
         gather_ok = None
-        if world > 1:
+        if world > 1 and args.full:
             ok = True
             if rank == 0:
                 ref = gathered[last].clone()
@@ -276,14 +295,15 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
 
     boundary = None
-    if rank == 0 and world == 1 and not cfg5 and not args.no_boundary and args.config == 3 and not variant:
+    if (args.full and rank == 0 and world == 1 and not cfg5 and not args.no_boundary and args.config == 3
+            and not variant):
         boundary = boundary_pass(cfg, B, S, T, args.steps, args.warmup, value)
     roofline, kernels = None, None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         roofline, kernels = roofline_pass(step, stream, dtype, vit_fp8, args.config)
     cpu = None
     n_cpu = B if args.cpu_images < 0 else args.cpu_images
-    if rank == 0 and world == 1 and n_cpu > 0:
+    if args.full and rank == 0 and world == 1 and n_cpu > 0:
         cpu = (cpu_baseline_sliding(arch, sd, text.cpu()) if cfg5 else
                cpu_baseline(arch, sd, text.cpu(), n_cpu))
     if rank == 0:
@@ -324,6 +344,23 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, suffix, arrays, whole_bytes=16 << 20, sample=4 << 20):
+    """--dump-outputs: each device tensor as DIR/<name><suffix>.npy in fp32.  An array over `whole_bytes`
+    is written as a fixed sample of `sample` of its elements (flat indices drawn once from a seeded
+    generator and sorted: the same elements in every run of the same arguments), so a dump stays
+    under 64 MB (two arrays of at most 16 MiB each)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() * 4 > whole_bytes:
+            gen = torch.Generator().manual_seed(20240 + len(name))
+            idx = torch.randint(0, flat.numel(), (sample,), generator=gen).sort()[0]
+            a = flat[idx.to(flat.device)].float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def boundary_pass(cfg, B, S, T, steps, warmup, engine_value):

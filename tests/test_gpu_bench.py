@@ -30,7 +30,7 @@ def _bench(*args, timeout=400):
 def test_bench_two_ranks_gloo_on_one_gpu():
     # 3 timed steps after 1 warm-up: both graphs of the two-buffer ring replay, and the gate checks
     # the last step's gathered logits (ring slot 1)
-    line = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-images", "0", "--no-roofline",
+    line = _bench("--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-images", "0", "--no-roofline",
                   "--backend", "gloo")
     assert line["n_gpus"] == 2 and line["ranks"] == 2 and line["backend"] == "gloo"
     assert line["gather_matches_1gpu"] is True
@@ -43,15 +43,15 @@ def test_bench_two_ranks_gloo_on_one_gpu():
 def test_bench_config5_two_ranks_gloo_on_one_gpu():
     """Config 5 (sliding 640², fp8 ViT GEMMs) batch-sharded over 2 ranks: every rank all-gathers the
     crops' head logits (5 planes per image), rank 0 re-runs both ranks' images bit for bit."""
-    line = _bench("--config", "5", "--gpus", "2", "--batch", "1", "--classes", "64", "--steps", "2", "--warmup", "1",
-                  "--cpu-images", "0", "--no-roofline", "--backend", "gloo")
+    line = _bench("--full", "--config", "5", "--gpus", "2", "--batch", "1", "--classes", "64", "--steps", "2",
+                  "--warmup", "1", "--cpu-images", "0", "--no-roofline", "--backend", "gloo")
     assert line["n_gpus"] == 2 and line["gather_matches_1gpu"] is True
     assert line["config"]["bench_config"] == 5 and line["config"]["global_batch"] == 2
 
 
 @pytest.mark.timeout(400)
 def test_bench_one_gpu_line_contract():
-    line = _bench("--steps", "2", "--warmup", "1", "--cpu-images", "0")
+    line = _bench("--full", "--steps", "2", "--warmup", "1", "--cpu-images", "0")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
               "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in line, k

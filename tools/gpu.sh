@@ -29,20 +29,20 @@ tests() {
   timeout -k 10 900 python -u -m pytest "$@" -x -v --timeout 400 --timeout-method thread > "$O/tests.log" 2>&1
 }
 bench() {
-  if [ $# -eq 0 ]; then set -- --cpu-images 0; fi
+  if [ $# -eq 0 ]; then set -- --full --cpu-images 0; fi
   timeout -k 10 400 python -u bench.py "$@" > "$O/bench.json" 2> "$O/bench.err"
 }
 configs() {
-  timeout -k 10 300 python -u bench.py --config 2 --cpu-images 0 > "$O/bench_config2.json" 2>> "$O/bench.err" &&
-  timeout -k 10 300 python -u bench.py --config 4 --cpu-images 0 > "$O/bench_config4.json" 2>> "$O/bench.err" &&
-  timeout -k 10 400 python -u bench.py --config 5 --steps 3 --warmup 1 --cpu-images 0 > "$O/bench_config5.json" 2>> "$O/bench.err"
+  timeout -k 10 300 python -u bench.py --full --config 2 --cpu-images 0 > "$O/bench_config2.json" 2>> "$O/bench.err" &&
+  timeout -k 10 300 python -u bench.py --full --config 4 --cpu-images 0 > "$O/bench_config4.json" 2>> "$O/bench.err" &&
+  timeout -k 10 400 python -u bench.py --full --config 5 --steps 3 --warmup 1 --cpu-images 0 > "$O/bench_config5.json" 2>> "$O/bench.err"
 }
 train() {
   timeout -k 10 600 python -u tools/bench_train.py --profile "$@" > "$O/bench_train.json" 2> "$O/bench_train.err"
 }
 trace() {
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$O/trace" -o run -- \
-    python3 "$R/bench.py" --steps 5 --warmup 2 --cpu-images 0 > "$O/trace.log" 2>&1)
+    python3 "$R/bench.py" --full --steps 5 --warmup 2 --cpu-images 0 > "$O/trace.log" 2>&1)
 }
 pmc() {
   (cd /tmp &&
@@ -86,7 +86,7 @@ case "$CMD" in
   micro) micro "$@" ;;
   smoke) smoke ;;
   final) tests && smoke && bench && configs && trace && pmc "$@" && sq ;;
-  final1) tests && smoke && bench --cpu-images -1 && configs ;;
+  final1) tests && smoke && bench --full --cpu-images -1 && configs ;;
   final2) trace && pmc "$@" && sq && train ;;
   *) echo "unknown command $CMD" >&2; exit 2 ;;
 esac
