@@ -565,10 +565,15 @@ __global__ __launch_bounds__(NW * 64, (2 * NW + 3) / 4) void vit_attn3_kernel(At
 
 int g_attn_store = 1;   // vit_attn3 output stores: 0 = plain, 1 = sc1 write-through (same box, whole step: 9.232 -> 9.175 ms)
 CATSEG_KNOB(g_attn_store, "attn_store");
+int g_attn_last_wt = 0;   // read-only diagnostic (tests): 1 = the last vit_attn3 launch used write-through stores
+CATSEG_KNOB(g_attn_last_wt, "attn_last_wt");
 template <int NW, int QT, bool L2S = false>
 void launch_vit3(const AttnP& p, hipStream_t st) {
   dim3 grid((unsigned)((p.L + 16 * NW * QT - 1) / (16 * NW * QT)), (unsigned)(p.n_seq * p.H));
-  if (g_attn_store) hipLaunchKernelGGL((vit_attn3_kernel<NW, QT, L2S, true>), grid, dim3(NW * 64), 0, st, p);
+  // write-through only when every byte offset of the output fits its 31-bit offset
+  const bool wt = g_attn_store && wt_fits((int64_t)p.n_seq * p.L * p.ldo, 2);
+  g_attn_last_wt = wt;
+  if (wt) hipLaunchKernelGGL((vit_attn3_kernel<NW, QT, L2S, true>), grid, dim3(NW * 64), 0, st, p);
   else hipLaunchKernelGGL((vit_attn3_kernel<NW, QT, L2S>), grid, dim3(NW * 64), 0, st, p);
 }
 
@@ -657,6 +662,7 @@ extern "C" int catseg_attention(const CatsegAttnArgs* a, void* stream) {
     CATSEG_CHECK(a->mode == 0, "attention: bad mode");
   }
   hipStream_t st = (hipStream_t)stream;
+  g_attn_last_wt = 0;   // launch_vit3 sets it
   int rc = a->dtype == CATSEG_BF16 ? dispatch<bf16>(p, a->head_dim, st)
                                    : dispatch<float>(p, a->head_dim, st);
   CATSEG_CHECK(rc == 0, "attention: unsupported head_dim/mode combination");

@@ -444,6 +444,21 @@ int g_gemm3_store = 0;  // gemm3 lean fp32 epilogue stores: 0 = plain, 1 = nt (A
 // tools/ab_knob.py: 9.309 / 9.286 / 9.234 ms)
 int g_wide_store = 2;
 int g_wide_epi = 1;   // gemm6 bf16 outputs: 1 = register-side epilogue (wide_epilogue_bf16), 0 = fp32 LDS staging
+// read-only diagnostics (tests): the kernel of the last launch -- the variant number of a gemm3 / gemm6
+// tile, 2 = gemm2_kernel, 3 = the generic gemm_kernel -- and whether it took a write-through store form
+int g_gemm_last = 0;
+int g_gemm_last_wt = 0;
+// gemm3's lean one-or-two-items-per-thread epilogue (the only gemm3 path with the gemm3_store forms):
+// the kernel's own condition, shared with launch3 so that gemm_last_wt reports what the kernel does
+template <int BM, int BN, int WGM, int WGN, int EPI, bool SC>
+struct Gemm3Lean {
+  static constexpr int NT3 = 64 * WGM * WGN, FM = BM / WGM / 16;
+  static constexpr int JR0 = 4 / WGM, JR = FM % JR0 == 0 ? JR0 : (JR0 >= 2 && FM % 2 == 0 ? 2 : 1);
+  static constexpr int ROWS = WGM * JR * 16;
+  static constexpr int IPT = ROWS * (BN / 8) / NT3;   // output items per thread per round
+  static constexpr bool ONE = IPT >= 1 && IPT <= 2 && ROWS * (BN / 8) == IPT * NT3 && NT3 % (BN / 8) == 0 && EPI != 0 &&
+                              !SC;
+};
 template <typename TO, int BM, int BN, int WGM, int WGN, int S, int BK, bool F8 = false, bool SC = false,
           int EPI = 0>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm3_kernel(const bf16* __restrict__ A, int64_t lda, RowMap amap,
@@ -593,9 +608,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm3_kernel(const bf16* __res
   // requested before round h's barrier, so no round waits for its own global loads (the loop
   // below issues them inside each round: one HBM round trip per round, ~5 rounds per tile)
   // IPT = output items per thread per round; every item of a thread has the same 8 columns
-  constexpr int IPT = ROWS * (BN / 8) / NT3;
-  constexpr bool ONE = IPT >= 1 && IPT <= 2 && ROWS * (BN / 8) == IPT * NT3 && NT3 % (BN / 8) == 0 && EPI != 0 &&
-                       !SC;
+  using Lean = Gemm3Lean<BM, BN, WGM, WGN, EPI, SC>;
+  static_assert(Lean::ROWS == ROWS, "Gemm3Lean mirrors the epilogue rounds");
+  constexpr int IPT = Lean::IPT;
+  constexpr bool ONE = Lean::ONE;
   if constexpr (ONE) {
     if (e.pf & 1) {
       const int c8 = (tid % (BN / 8)) * 8;
@@ -1026,7 +1042,9 @@ __global__ __launch_bounds__(512) void gemm6_kernel(const bf16* __restrict__ A, 
 
 int g_gemm_group = 4;   // gemm3 tile order: 0 = row-major, G > 0 = G m-tiles per group (catseg_set_gemm_group); 4 measured best (fc2 48.6 -> 47.4 us)
 
-EpiArgs make_epi(const CatsegGemmArgs* g) {
+// out_bytes = sizeof(TO): the write-through store forms (pf bits 8 / 32) carry a 31-bit byte offset, so
+// an output whose extent does not fit falls to the kernels' plain-store branch
+EpiArgs make_epi(const CatsegGemmArgs* g, int out_bytes) {
   EpiArgs e;
   e.bias = g->bias;
   e.add = g->add; e.ld_add = g->ld_add; e.add_ncols = g->add_ncols;
@@ -1039,6 +1057,8 @@ EpiArgs make_epi(const CatsegGemmArgs* g) {
   e.sa = nullptr; e.sw = nullptr;
   e.pf = g_epi_prefetch | (g_wide_epi ? 2 : 0) | (g_wide_store == 1 ? 4 : g_wide_store == 2 ? 8 : 0) |
          (g_gemm3_store == 1 ? 16 : g_gemm3_store == 2 ? 32 : 0);
+  const int64_t out_elems = g->store_mode == 0 ? g->M * g->ldo : g->M * g->N;   // scatter: M x k x k x cout, dense
+  if (!wt_fits(out_elems, out_bytes)) e.pf &= ~(8 | 32);
   return e;
 }
 
@@ -1050,20 +1070,30 @@ bool launch6(const CatsegGemmArgs* g, hipStream_t st) {
   if (g->N % BN != 0 || g->K % 64 != 0) return false;
   const bool ident = g->amap.d1 == 1 && g->amap.m1 >= g->M && g->amap.s1 == 1 && g->amap.m2 == 1 && g->amap.off == 0;
   if (!ident) return false;
-  const EpiArgs e = make_epi(g);
+  const EpiArgs e = make_epi(g, sizeof(TO));
   const int tm = (int)((g->M + BM - 1) / BM), tn = (int)(g->N / BN);
   auto kern = gemm6_kernel<TO, BM, BN, EPI, ABL>;
+  g_gemm_last = ABL == 0 ? (BM == 320 ? (BN == 256 ? 50 : 51) : 52) : (BM == 256 ? 55 + ABL : 57 + ABL);
+  // the kernel's choice of wide_epilogue_bf16, whose stores are the only ones with a write-through form
+  g_gemm_last_wt = sizeof(TO) == 2 && (BM / 32) % 2 == 0 && (e.pf & 2) && !(EPI == 1 && e.res) && !(e.pf & 4) && (e.pf & 8);
   hipLaunchKernelGGL(kern, dim3((unsigned)(tm * tn)), dim3(512), 0, st, (const bf16*)g->A, g->lda, (const bf16*)g->W,
                      g->ldw, g->M, g->K, tn, e, std::max(1, g_gemm4_group));
   return true;
 }
 
+// the gemm_variant number of a gemm3 tile (try_gemm3's table)
+constexpr int gemm3_variant(int bm, int bn, int s, int bk) {
+  return bm == 256 ? 1 : bm == 224 ? 20 : bm == 128 ? 19 : bm == 96 ? 24 : s == 3 ? 21 : s == 4 ? 22 : bk == 128 ? 15 : 17;
+}
+
 template <typename TO, int BM, int BN, int WGM, int WGN, int S, int BK, bool SC = false, int EPI = 0>
 bool launch3(const CatsegGemmArgs* g, hipStream_t st) {
   if (g->N % BN != 0 || g->K % BK != 0) return false;
-  const EpiArgs e = make_epi(g);
+  const EpiArgs e = make_epi(g, sizeof(TO));
   RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
   const int tm = (int)((g->M + BM - 1) / BM), tn = (int)(g->N / BN);
+  g_gemm_last = gemm3_variant(BM, BN, S, BK);
+  g_gemm_last_wt = Gemm3Lean<BM, BN, WGM, WGN, EPI, SC>::ONE && (e.pf & 1) && sizeof(TO) == 4 && !(e.pf & 16) && (e.pf & 32);
   hipLaunchKernelGGL((gemm3_kernel<TO, BM, BN, WGM, WGN, S, BK, false, SC, EPI>), dim3((unsigned)(tm * tn)), dim3(64 * WGM * WGN), 0,
                      st, (const bf16*)g->A, g->lda, am, (const bf16*)g->W, g->ldw, g->M, g->K, tn, e, g_gemm_group);
   return true;
@@ -1073,7 +1103,7 @@ bool launch3(const CatsegGemmArgs* g, hipStream_t st) {
 template <typename TO, int BM, int BN, int WGM, int WGN, int S, int BK, int EPI = 0>
 bool launch3f8(const CatsegGemmArgs* g, const float* sa, const float* sw, hipStream_t st) {
   if (g->N % BN != 0 || (g->K / 2) % BK != 0) return false;
-  EpiArgs e = make_epi(g);
+  EpiArgs e = make_epi(g, sizeof(TO));
   e.sa = sa; e.sw = sw;
   RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
   const int tm = (int)((g->M + BM - 1) / BM), tn = (int)(g->N / BN);
@@ -1197,6 +1227,8 @@ void launch(const CatsegGemmArgs* g, hipStream_t st) {
   e.cvt_cout = g->cvt_cout;
   RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
   dim3 grid((unsigned)((g->M + BM - 1) / BM), (unsigned)((g->N + BN - 1) / BN));
+  g_gemm_last = 3;
+  g_gemm_last_wt = 0;
   hipLaunchKernelGGL((gemm_kernel<TA, TO, BM, BN>), grid, dim3(NT), 0, st,
                      (const TA*)g->A, g->lda, am, (const TA*)g->W, g->ldw, g->M, g->N, g->K, e);
 }
@@ -1214,6 +1246,8 @@ void launch2(const CatsegGemmArgs* g, hipStream_t st) {
   e.cvt_cout = g->cvt_cout;
   RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
   const int tm = (int)((g->M + BM - 1) / BM), tn = (int)((g->N + BN - 1) / BN);
+  g_gemm_last = 2;
+  g_gemm_last_wt = 0;
   hipLaunchKernelGGL((gemm2_kernel<TO, BM, BN>), dim3((unsigned)(tm * tn)), dim3(NT), 0, st, (const bf16*)g->A,
                      g->lda, am, (const bf16*)g->W, g->ldw, g->M, g->N, g->K, tn, e);
 }
@@ -1284,6 +1318,8 @@ CATSEG_KNOB(g_epi_prefetch, "epi_prefetch");
 CATSEG_KNOB(g_wide_epi, "wide_epi");
 CATSEG_KNOB(g_wide_store, "wide_store");
 CATSEG_KNOB(g_gemm3_store, "gemm3_store");
+CATSEG_KNOB(g_gemm_last, "gemm_last");
+CATSEG_KNOB(g_gemm_last_wt, "gemm_last_wt");
 CATSEG_KNOB(g_gemm_f8_variant, "gemm_fp8_variant");
 
 extern "C" int catseg_gemm_fp8(const CatsegGemmArgs* g, const float* scale_a, const float* scale_w, void* stream) {

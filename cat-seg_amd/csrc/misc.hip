@@ -171,6 +171,10 @@ int g_ln_variant = 0;   // 0 = pipelined persistent fp32 -> bf16 LayerNorm where
 CATSEG_KNOB(g_ln_variant, "ln_variant");
 int g_ln_store = 1;     // ln_pipe stores: 0 = plain, 1 = sc1 write-through (same box, whole step: 9.445 -> 9.385 ms)
 CATSEG_KNOB(g_ln_store, "ln_store");
+// read-only diagnostic (tests): the kernel of the last rownorm launch, 0 = rownorm_kernel, 1 = ln_pipe with
+// plain stores, 2 = ln_pipe with write-through stores
+int g_ln_last = 0;
+CATSEG_KNOB(g_ln_last, "ln_last");
 
 template <bool LN>
 int rownorm(const void* in, int64_t ld_in, CatsegRowMap m, int dti, void* out, int64_t ld_out, int dto,
@@ -188,8 +192,11 @@ int rownorm(const void* in, int64_t ld_in, CatsegRowMap m, int dti, void* out, i
     // 2 waves per SIMD over the 256 CUs: ~2-5 rows per wave at the ViT's 2308-4616 rows
     const int64_t cap = g_ln_variant == 2 ? 256 : g_ln_variant == 3 ? 1024 : 512;
     const unsigned pg = (unsigned)std::min<int64_t>((rows + 3) / 4, cap);
-    if (g_ln_store) hipLaunchKernelGGL((ln_pipe_kernel<4, true>), dim3(pg), block, 0, st, (const float*)in, ld_in, rm, (bf16*)out, ld_out,
-                                       gamma, beta, rows, eps);
+    // write-through only when every byte offset of the output fits its 31-bit offset
+    const bool wt = g_ln_store && wt_fits(rows * ld_out, 2);
+    g_ln_last = wt ? 2 : 1;
+    if (wt) hipLaunchKernelGGL((ln_pipe_kernel<4, true>), dim3(pg), block, 0, st, (const float*)in, ld_in, rm, (bf16*)out, ld_out,
+                               gamma, beta, rows, eps);
     else hipLaunchKernelGGL((ln_pipe_kernel<4>), dim3(pg), block, 0, st, (const float*)in, ld_in, rm, (bf16*)out, ld_out,
                        gamma, beta, rows, eps);
     return catseg_launch_status("layernorm");
@@ -197,6 +204,7 @@ int rownorm(const void* in, int64_t ld_in, CatsegRowMap m, int dti, void* out, i
 #define RN_LAUNCH(TI, TO)                                                                                   \
   hipLaunchKernelGGL((rownorm_kernel<TI, TO, LN>), grid, block, 0, st, (const TI*)in, ld_in, rm, (TO*)out, \
                      ld_out, gamma, beta, rows, (int)cols, eps)
+  g_ln_last = 0;
   if (dti == CATSEG_F32 && dto == CATSEG_F32) RN_LAUNCH(float, float);
   else if (dti == CATSEG_F32 && dto == CATSEG_BF16) RN_LAUNCH(float, bf16);
   else if (dti == CATSEG_BF16 && dto == CATSEG_BF16) RN_LAUNCH(bf16, bf16);

@@ -4,6 +4,9 @@
  * picks its tiling / variant automatically; these knobs force an alternative for same-process
  * A/B timing (tools/) and for the tests that prove every alternative computes the same bits.
  * Knobs are process-wide and read at launch time (so at hipGraph capture).
+ * The names ending in _last / _last_wt (gemm_last, gemm_last_wt, ln_last, attn_last_wt) are read-only
+ * diagnostics: the launch writes which kernel / store form it chose, so a test that forces a variant
+ * can see that the kernel it names ran; setting them changes nothing.
  */
 #ifndef CATSEG_HIP_TUNING_H
 #define CATSEG_HIP_TUNING_H

@@ -104,6 +104,7 @@ def test_gemm_convtranspose_store_pipelined(cout, k):
     out = torch.full((S * H * k * Wd * k, cout), float("nan"), device=dev, dtype=torch.bfloat16)
     ops.gemm(A.to(dev, torch.bfloat16).contiguous(), Wg.to(dev, torch.bfloat16).contiguous(), out,
              bias=b.repeat(k * k).to(dev), store=(k, H, Wd, cout))
+    assert L.tuning("gemm_last") in (15, 17)     # the scatter epilogue's two tiles (try_gemm3)
     got = out.reshape(S, H * k, Wd * k, cout).permute(0, 3, 1, 2)
     close(got, ref, atol=2e-2, rtol=1e-2, what=f"convT pipelined cout {cout} k {k}")
 
@@ -126,8 +127,11 @@ def test_gemm_epilogue_prefetch(variant):
             L.tune("epi_prefetch", pf)
             o1 = torch.full((M, N), float("nan"), device=dev)
             ops.gemm(A, W, o1, bias=b, res=res)
+            last1 = L.tuning("gemm_last")
             o2 = torch.full((M, N), float("nan"), device=dev, dtype=torch.bfloat16)
             ops.gemm(A, W, o2, bias=b, act=L.ACT_QUICKGELU)
+            if variant:                                   # the forced tile ran, not a silent fall-back
+                assert last1 == variant and L.tuning("gemm_last") == variant
             torch.cuda.synchronize()
             outs[pf] = (o1, o2)
     finally:
@@ -157,6 +161,7 @@ def test_gemm_pipelined_variants(variant):
             r = res.to(dev, odt)
             ops.gemm(A.to(dev, torch.bfloat16), W.to(dev, torch.bfloat16), out, M=M, bias=b.to(dev), act=act,
                      res=r, amap=amap)
+            assert L.tuning("gemm_last") == variant       # the forced tile ran, not a silent fall-back
             v = arow.to(torch.bfloat16).double() @ W.to(torch.bfloat16).double().T + b.double()
             if act == L.ACT_QUICKGELU:
                 v = v * torch.sigmoid(1.702 * v)
