@@ -177,6 +177,27 @@ class LinAttnBwdArgs(C.Structure):
     ]
 
 
+class FullAttnBwdArgs(C.Structure):
+    _fields_ = [
+        ("q", vp), ("k", vp), ("v", vp), ("ld_qkv", i64),
+        ("dy", vp), ("ld_dy", i64),
+        ("dq", vp), ("dk", vp), ("dv", vp), ("ld_dqkv", i64),
+        ("B", i64), ("T", i32), ("HW", i32), ("n_heads", i32), ("head_dim", i32), ("scale", f32),
+        ("n_pad", i32), ("k_pad", vp), ("v_pad", vp),
+        ("dk_pad", vp), ("dv_pad", vp),
+        ("workspace", vp), ("workspace_bytes", i64),
+    ]
+
+
+class FullAttnTrainFwdArgs(C.Structure):
+    _fields_ = [
+        ("q", vp), ("k", vp), ("v", vp), ("ld_qkv", i64),
+        ("x", vp), ("y", vp), ("ld_xy", i64),
+        ("B", i64), ("T", i32), ("HW", i32), ("n_heads", i32), ("head_dim", i32), ("scale", f32),
+        ("n_pad", i32), ("k_pad", vp), ("v_pad", vp),
+    ]
+
+
 class Conv2dArgs(C.Structure):
     _fields_ = [
         ("x", vp), ("ld_x", i64),
@@ -272,6 +293,9 @@ _SIGS = {
     "catseg_attention_backward_workspace": [i64, i32, i32],
     "catseg_linear_attention_backward": [C.POINTER(LinAttnBwdArgs), vp],
     "catseg_linear_attention_backward_workspace": [i64, i32],
+    "catseg_full_attention_backward": [C.POINTER(FullAttnBwdArgs), vp],
+    "catseg_full_attention_backward_workspace": [i64, i32, i32, i32, i32],
+    "catseg_full_attention_train_forward": [C.POINTER(FullAttnTrainFwdArgs), vp],
     "catseg_conv2d_nhwc": [C.POINTER(Conv2dArgs), vp],
     "catseg_conv2d_wgrad": [C.POINTER(Conv2dArgs), vp],
     "catseg_conv2d_wgrad_workspace": [C.POINTER(Conv2dArgs)],

@@ -263,6 +263,47 @@ def linear_attention_backward(qkv, dy, dqkv, *, B, T, HW, n_heads, head_dim, n_p
     return dqkv
 
 
+def full_attention_forward(qkv, x, y, *, B, T, HW, n_heads, head_dim, n_pad=0, k_pad=None, v_pad=None):
+    """y = x + FullAttention(q, k, v) on the class-major rows for the training step
+    (catseg_full_attention_train_forward: fp32 in / out, scores on the f64 MFMA)."""
+    _chk(qkv, x, y, k_pad, v_pad)
+    D = n_heads * head_dim
+    a = L.FullAttnTrainFwdArgs()
+    a.q, a.k, a.v, a.ld_qkv = qkv.data_ptr(), qkv[:, D:].data_ptr(), qkv[:, 2 * D:].data_ptr(), qkv.stride(0)
+    a.x, a.y, a.ld_xy = x.data_ptr(), y.data_ptr(), x.stride(0)
+    assert y.stride(0) == x.stride(0)
+    a.B, a.T, a.HW, a.n_heads, a.head_dim, a.scale = B, T, HW, n_heads, head_dim, head_dim ** -0.5
+    a.n_pad = n_pad
+    if n_pad > 0:
+        a.k_pad, a.v_pad = k_pad.data_ptr(), v_pad.data_ptr()
+    with _rec("full_attention_train_forward", 6 * B * HW * n_heads * T * (T + 1) * head_dim):
+        call("catseg_full_attention_train_forward", a, _stream())
+    return y
+
+
+def full_attention_backward(qkv, dy, dqkv, *, B, T, HW, n_heads, head_dim, n_pad=0, k_pad=None, v_pad=None,
+                            dk_pad=None, dv_pad=None):
+    """dq | dk | dv of ATTENTION_TYPE "full" on the class-major rows (b*T + t)*HW + p
+    (catseg_full_attention_backward): softmax over a pixel's T classes and the n_pad padding keys
+    (k_pad / v_pad), whose gradients go to dk_pad / dv_pad; nothing saved from the forward."""
+    _chk(qkv, dy, dqkv, k_pad, v_pad, dk_pad, dv_pad)
+    D = n_heads * head_dim
+    a = L.FullAttnBwdArgs()
+    a.q, a.k, a.v, a.ld_qkv = qkv.data_ptr(), qkv[:, D:].data_ptr(), qkv[:, 2 * D:].data_ptr(), qkv.stride(0)
+    a.dy, a.ld_dy = dy.data_ptr(), dy.stride(0)
+    a.dq, a.dk, a.dv, a.ld_dqkv = dqkv.data_ptr(), dqkv[:, D:].data_ptr(), dqkv[:, 2 * D:].data_ptr(), dqkv.stride(0)
+    a.B, a.T, a.HW, a.n_heads, a.head_dim, a.scale = B, T, HW, n_heads, head_dim, head_dim ** -0.5
+    a.n_pad = n_pad
+    ws = None
+    if n_pad > 0:
+        a.k_pad, a.v_pad, a.dk_pad, a.dv_pad = k_pad.data_ptr(), v_pad.data_ptr(), dk_pad.data_ptr(), dv_pad.data_ptr()
+        ws = _ws(L.load().catseg_full_attention_backward_workspace(B, T, HW, n_heads, n_pad), qkv.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    with _rec("full_attention_backward", 10 * B * HW * n_heads * T * (T + 1) * head_dim):
+        call("catseg_full_attention_backward", a, _stream())
+    return dqkv
+
+
 def _conv_args(x, w, y, *, S, H, W, cin, cout, ksize, bias=None, act=L.ACT_NONE, alpha=1.0, beta=0, ld_x=None,
                ld_y=None, ld_w=None, dw=None):
     a = L.Conv2dArgs()

@@ -346,6 +346,7 @@ class Geo:
     H: int
     W: int
     nh: int
+    attn: str = "linear"        # ATTENTION_TYPE of the class layers
 
 
 class SwinBlockFn(torch.autograd.Function):
@@ -427,8 +428,8 @@ class SwinBlockFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------- class layer
 class ClassLayerFn(torch.autograd.Function):
     """ClassTransformerLayer.forward (model.py:387-424): x_pool = AvgPool(x), padded with the learned
-    padding token / guidance to pad_len classes (model.py:397-410); x_pool += LinearAttn(LN1(x_pool),
-    text guidance); x_pool += MLP(LN2(x_pool)); x + bilinear_align_corners(x_pool) cropped to T.
+    padding token / guidance to pad_len classes (model.py:397-410); x_pool += Attn(LN1(x_pool),
+    text guidance), Attn = LinearAttention or FullAttention by geo.attn (model.py:331-334); x_pool += MLP(LN2(x_pool)); x + bilinear_align_corners(x_pool) cropped to T.
     X rows [B*T*HW][D], tg [T][Dt] (text_guidance_projection output, shared by the images)."""
 
     @staticmethod
@@ -467,8 +468,12 @@ class ClassLayerFn(torch.autograd.Function):
         y = torch.empty_like(Xp)
         kp = kvp[0, D:2 * D].contiguous() if n_pad else None
         vp = kvp[0, 2 * D:].contiguous() if n_pad else None
-        ops.linear_attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], Xp, y, B=geo.B, T=geo.T, HW=HWc,
-                             n_heads=geo.nh, head_dim=D // geo.nh, n_pad=n_pad, k_pad=kp, v_pad=vp)
+        if geo.attn == "full":      # fp32 rows, scores on the f64 MFMA (the eval path keeps ops.full_attention)
+            TO.full_attention_forward(qkv, Xp, y, B=geo.B, T=geo.T, HW=HWc, n_heads=geo.nh, head_dim=D // geo.nh,
+                                      n_pad=n_pad, k_pad=kp, v_pad=vp)
+        else:
+            ops.linear_attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], Xp, y, B=geo.B, T=geo.T, HW=HWc,
+                                 n_heads=geo.nh, head_dim=D // geo.nh, n_pad=n_pad, k_pad=kp, v_pad=vp)
         h2 = torch.empty_like(y)
         ops.layernorm(y, n2w.detach(), n2b.detach(), h2)
         u = _empty(Rp, w0.shape[0], like=X)
@@ -512,13 +517,14 @@ class ClassLayerFn(torch.autograd.Function):
         dy = dyo.clone()
         dn2w, dn2b = _empty(D, like=Xp), _empty(D, like=Xp)
         TO.layernorm_backward(y, n2w.detach(), dh2, dy, acc_dx=True, dgamma=dn2w, dbeta=dn2b)
-        # y = Xp + LinearAttention(q, k, v)
+        # y = Xp + LinearAttention(q, k, v) or Xp + FullAttention(q, k, v)
         dqkv = _empty(Rp, 3 * D, like=Xp)
         dkp = dvp = None
         if n_pad:
             dkp, dvp = _empty(D, like=Xp), _empty(D, like=Xp)
-        TO.linear_attention_backward(qkv, dy, dqkv, B=geo.B, T=geo.T, HW=HWc, n_heads=geo.nh, head_dim=D // geo.nh,
-                                     n_pad=n_pad, k_pad=kp, v_pad=vp, dk_pad=dkp, dv_pad=dvp)
+        attn_bwd = TO.full_attention_backward if geo.attn == "full" else TO.linear_attention_backward
+        attn_bwd(qkv, dy, dqkv, B=geo.B, T=geo.T, HW=HWc, n_heads=geo.nh, head_dim=D // geo.nh, n_pad=n_pad,
+                 k_pad=kp, v_pad=vp, dk_pad=dkp, dv_pad=dvp)
         wx, _, wt = _qkv_split(qw, qb, kw, kb, vw, vb, D)
         dwx, dbx = _mm_t(dqkv, h), _colsum(dqkv)
         dh = TO.mm(dqkv, wx)
@@ -946,8 +952,8 @@ def head_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], feats: torc
     if a.vpt:
         raise NotImplementedError("training step: visual prompt tuning is not built (frozen-CLIP features "
                                   "carry the prompt rows)")
-    if a.attention_type != "linear":
-        raise NotImplementedError("training step: ATTENTION_TYPE 'linear' only (the full-attention backward is not built)")
+    if a.attention_type not in ("linear", "full"):
+        raise NotImplementedError(f"training step: unknown ATTENTION_TYPE {a.attention_type!r}")
     G = a.grid
     HW = G * G
     B = feats.shape[0] // (HW + 1)
@@ -956,7 +962,7 @@ def head_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], feats: torc
         raise NotImplementedError("training with more classes than pad_len (top-k selection) is not built")
     if a.hidden_dim != 128 or a.nheads != 4:
         raise NotImplementedError("HIP training path: hidden_dim 128 / 4 heads only")
-    geo = Geo(B=B, T=T, H=G, W=G, nh=a.nheads)
+    geo = Geo(B=B, T=T, H=G, W=G, nh=a.nheads, attn=a.attention_type)
     p = AGG
     # guidance maps (cat_seg_model.py:178-186): res3 = dense tokens, res4/res5 = ConvTranspose of the hooks
     res3 = DropClsFn.apply(feats, HW)

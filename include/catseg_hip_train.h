@@ -178,6 +178,44 @@ typedef struct {
 int catseg_linear_attention_backward(const CatsegLinAttnBwdArgs* args, void* stream);
 int64_t catseg_linear_attention_backward_workspace(int64_t B, int HW);
 
+/* catseg_full_attention_backward — FullAttention backward (ATTENTION_TYPE "full", model.py:289-320) for
+ * the class-major rows of the class aggregation: token t of sequence (b, p) at row (b*T + t)*HW + p, as
+ * catseg_linear_attention_backward (no packed copy).  q/k/v the forward projections (scale NOT applied),
+ * dy = dL/d(attention output); nothing else is kept from the forward (the softmax statistics are
+ * recomputed).  The n_pad learned padding tokens (model.py:397-410) are one extra key column
+ * (k_pad, v_pad, [heads*head_dim] as for catseg_class_seq_pack) of multiplicity n_pad in every
+ * softmax row; their own outputs are discarded by the reference, so there are no padding queries.
+ * Writes dq, dk, dv (rows t < T only); with n_pad > 0 also dk_pad / dv_pad [heads*head_dim], summed
+ * over the n_pad copies and every pixel.  4 heads x 32, 1 <= T <= 2048, strides % 4 == 0, q / k / v / dy
+ * 16-byte aligned.  workspace >= catseg_full_attention_backward_workspace bytes: B*HW*256 floats
+ * when n_pad > 0, else 0. */
+typedef struct {
+  const void* q; const void* k; const void* v; int64_t ld_qkv;
+  const void* dy; int64_t ld_dy;
+  void* dq; void* dk; void* dv; int64_t ld_dqkv;
+  int64_t B; int T; int HW; int n_heads; int head_dim; float scale;
+  int n_pad; const float* k_pad; const float* v_pad;
+  float* dk_pad; float* dv_pad;
+  void* workspace; int64_t workspace_bytes;
+} CatsegFullAttnBwdArgs;
+int catseg_full_attention_backward(const CatsegFullAttnBwdArgs* args, void* stream);
+int64_t catseg_full_attention_backward_workspace(int64_t B, int T, int HW, int n_heads, int n_pad);
+
+/* catseg_full_attention_train_forward — the training step's forward of the same attention on the same
+ * rows: y = x + softmax(scale q k^T) v (x, y rows as q, stride ld_xy; y may be x), the n_pad padding keys
+ * as one key of weight n_pad.  fp32 in and out; the scores are formed on the f64 MFMA (exact products
+ * and sums of the fp32 inputs), because peaked softmax rows multiply a score's fp32 rounding by the
+ * exponential and the step's gradients amplify it.  The eval path keeps catseg_class_seq_pack ->
+ * catseg_attention -> catseg_class_seq_unpack_add.  4 heads x 32, strides % 4 == 0, q / k / v 16-byte
+ * aligned; no workspace. */
+typedef struct {
+  const void* q; const void* k; const void* v; int64_t ld_qkv;
+  const void* x; void* y; int64_t ld_xy;
+  int64_t B; int T; int HW; int n_heads; int head_dim; float scale;
+  int n_pad; const float* k_pad; const float* v_pad;
+} CatsegFullAttnTrainFwdArgs;
+int catseg_full_attention_train_forward(const CatsegFullAttnTrainFwdArgs* args, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Convolutions (stride 1, pad = ksize / 2, NHWC)
  * ------------------------------------------------------------------------- */

@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--finetune", default="attention", choices=["attention", "none", "full"])
+    ap.add_argument("--attention-type", default="linear", choices=["linear", "full"],
+                    help="MODEL.SEM_SEG_HEAD.ATTENTION_TYPE of the class aggregation (model.py:331-334)")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--image", type=int, default=384,
                     help="training crop (the reference's INPUT.CROP.SIZE (384, 384) for B/16 and L/14; the "
@@ -43,6 +45,7 @@ def main():
     cfg.merge_from_file(os.path.join(ROOT, "cat-seg_amd", "configs", "vitb_384.yaml"))
     cfg.merge_from_list(["MODEL.SEM_SEG_HEAD.CLIP_PRETRAINED", a.clip, "MODEL.SEM_SEG_HEAD.POOLING_SIZES", "[2,2]",
                          "MODEL.SEM_SEG_HEAD.CLIP_FINETUNE", a.finetune, "MODEL.CATSEG_HIP.DTYPE", "f32",
+                         "MODEL.SEM_SEG_HEAD.ATTENTION_TYPE", a.attention_type,
                          "SOLVER.BASE_LR", "0.0002", "SOLVER.CLIP_GRADIENTS.ENABLED", "True",
                          "SOLVER.CLIP_GRADIENTS.CLIP_TYPE", "full_model", "SOLVER.CLIP_GRADIENTS.CLIP_VALUE", "0.01"])
     if a.clip != "ViT-B/16":
@@ -80,7 +83,7 @@ def main():
            "loss": float(loss.detach()), "grad_norm": float(opt.last_grad_norm[0]),
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
            "config": {"clip": a.clip, "resolution": S, "clip_resolution": model.clip_resolution[0], "classes": a.classes, "batch": a.batch, "pooling": [2, 2],
-                      "clip_finetune": a.finetune, "optimizer": "AdamW (HIP) + full-model clip 0.01"}}
+                      "clip_finetune": a.finetune, "attention_type": a.attention_type, "optimizer": "AdamW (HIP) + full-model clip 0.01"}}
     if a.profile:
         ops.PROFILE = []
         step()
