@@ -16,7 +16,7 @@ from .data.dataset_mappers import (  # noqa: F401
     MaskFormerSemanticDatasetMapper)
 from .registry import META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY, build_model  # noqa: F401
 from .cat_seg_model import CATSeg  # noqa: F401
-from .test_time_augmentation import SemanticSegmentorWithTTA  # noqa: F401
+from .tta import SemanticSegmentorWithTTA  # noqa: F401  (test_time_augmentation's + the OUTPUT "labels" refusal)
 from .modeling.heads.cat_seg_head import CATSegHead  # noqa: F401
 from .modeling.transformer.cat_seg_predictor import CATSegPredictor  # noqa: F401
 from .arch import CatSegArch, VIT_B16, VIT_L14_336, TINY  # noqa: F401

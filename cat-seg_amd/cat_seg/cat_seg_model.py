@@ -5,6 +5,9 @@ cat_seg/cat_seg_model.py:18-229).
 same config keys, with `forward(batched_inputs: list[dict]) -> list[dict]`:
   input  {"image": (3, H, W) uint8/float 0-255 (CPU or device), optional "height", "width"}
   output {"sem_seg": (T, height, width) fp32 sigmoid probabilities on the model device}
+         or, with MODEL.CATSEG_HIP.OUTPUT "labels", {"sem_seg_labels": (height, width) int32 argmax
+         over the classes, "sem_seg_score": (height, width) fp32 its probability} from one fused
+         kernel that never writes the (T, height, width) volume
 The reference returns results for batched_inputs[0] only (cat_seg_model.py:227-229);
 this boundary returns one result per input image by default
 (MODEL.CATSEG_HIP.RETURN_ALL_IMAGES; set False for the reference's exact behaviour).
@@ -65,8 +68,11 @@ class CATSeg(nn.Module):
                  train_class_json: str, test_class_json: str, sliding_window: bool, clip_finetune: str,
                  backbone_multiplier: float, clip_pretrained: str, arch: Optional[CatSegArch] = None,
                  dtype: str = "bf16", return_all_images: bool = True, synthetic_seed: int = 0,
-                 vit_fp8: bool = False, graph: bool = True):
+                 vit_fp8: bool = False, graph: bool = True, output: str = "probs"):
         super().__init__()
+        if output not in ("probs", "labels"):
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
+        self.output = output
         self.backbone = backbone
         self.sem_seg_head = sem_seg_head
         self.size_divisibility = size_divisibility
@@ -128,6 +134,7 @@ class CATSeg(nn.Module):
             "synthetic_seed": int(hip.get("SYNTHETIC_SEED", 0)) if hip else 0,
             "vit_fp8": bool(hip.get("VIT_FP8", False)) if hip else False,
             "graph": bool(hip.get("GRAPH", True)) if hip else True,
+            "output": str(hip.get("OUTPUT", "probs")) if hip else "probs",
         }
 
     # ------------------------------------------------------------------ parameters
@@ -226,6 +233,15 @@ class CATSeg(nn.Module):
         sizes_dev = torch.tensor(sizes, dtype=torch.int32).to(dev, non_blocking=True)
         return (raw if on_dev else raw.to(dev, non_blocking=True)), sizes_dev, sizes
 
+    def _labels(self, logits: torch.Tensor, hw, crop) -> List[dict]:
+        """OUTPUT "labels": one catseg_postprocess_argmax launch for the images of `logits`, into fresh
+        tensors; each result holds views of them."""
+        n, dev = logits.shape[0], logits.device
+        labels = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.int32)
+        score = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.float32)
+        ops.postprocess_argmax(logits, labels, score, crop=crop)
+        return [{"sem_seg_labels": labels[i], "sem_seg_score": score[i]} for i in range(n)]
+
     def _forward_traced(self, batched_inputs: List[dict]):
         """The eval forward as dynamo traces it (torch.compile): the canvas staging in torch ops, the
         network as the one registered operator catseg::head_logits (custom_ops), the resize through
@@ -250,6 +266,10 @@ class CATSeg(nn.Module):
             ih, iw = sizes[i]
             h = int(batched_inputs[i].get("height", ih))
             w = int(batched_inputs[i].get("width", iw))
+            if self.output == "labels":
+                lab, sc = torch.ops.catseg.postprocess_argmax(logits[i:i + 1], h, w, min(res, ih), min(res, iw), True)
+                results.append({"sem_seg_labels": lab[0], "sem_seg_score": sc[0]})
+                continue
             out = torch.ops.catseg.postprocess(logits[i:i + 1], h, w, min(res, ih), min(res, iw))
             results.append({"sem_seg": out[0]})
         return results
@@ -335,11 +355,16 @@ class CATSeg(nn.Module):
         h_l, w_l = logits.shape[-2:]
         if n > 1 and len(set(outs)) == 1 and len(set(sizes[:n])) == 1:
             # one launch for the whole batch (the engine leg's form); each result is a view of it
+            if self.output == "labels":
+                return self._labels(logits[:n], outs[0], (min(h_l, sizes[0][0]), min(w_l, sizes[0][1])))
             out = torch.empty(n, logits.shape[1], outs[0][0], outs[0][1], device=dev)
             ops.postprocess(logits[:n], out, crop=(min(h_l, sizes[0][0]), min(w_l, sizes[0][1])))
             return [{"sem_seg": out[i]} for i in range(n)]
         results = []
         for i in range(n):
+            if self.output == "labels":
+                results += self._labels(logits[i:i + 1], outs[i], (min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))
+                continue
             out = torch.empty(1, logits.shape[1], outs[i][0], outs[i][1], device=dev)
             ops.postprocess(logits[i:i + 1], out, crop=(min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))
             results.append({"sem_seg": out[0]})
@@ -366,6 +391,9 @@ class CATSeg(nn.Module):
                 ih, iw = sizes[i]
                 h = int(batched_inputs[i].get("height", ih))
                 w = int(batched_inputs[i].get("width", iw))
+                if self.output == "labels":
+                    results += self._labels(logits[i:i + 1], (h, w), (min(h_l, ih), min(w_l, iw)))
+                    continue
                 out = torch.empty(1, logits.shape[1], h, w, device=eng.device)
                 ops.postprocess(logits[i:i + 1], out, crop=(min(h_l, ih), min(w_l, iw)))
                 results.append({"sem_seg": out[0]})
@@ -411,6 +439,9 @@ class CATSeg(nn.Module):
             raw, sizes_dev, _ = self._batch(eng, [x["image"] for x in inputs])
             res = eng.SLIDE_OUT
             out_hw = [(int(x.get("height", res)), int(x.get("width", res))) for x in inputs]
+            if self.output == "labels":
+                return [{"sem_seg_labels": lab, "sem_seg_score": sc}
+                        for lab, sc in eng.forward_sliding(raw, sizes_dev, out_hw, labels=True)]
             return [{"sem_seg": o} for o in eng.forward_sliding(raw, sizes_dev, out_hw)]
 
 

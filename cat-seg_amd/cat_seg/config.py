@@ -191,4 +191,7 @@ def add_cat_seg_config(cfg):
     cfg.MODEL.CATSEG_HIP.SYNTHETIC_SEED = 0      # weights when MODEL.WEIGHTS is empty
     cfg.MODEL.CATSEG_HIP.VIT_FP8 = False         # config 5: e4m3 CLIP image-encoder GEMMs (bf16 engine)
     cfg.MODEL.CATSEG_HIP.GRAPH = True            # eval forward replayed from a hipGraph per input geometry
+    # eval output: "probs" {"sem_seg": (T, H, W) fp32} | "labels" {"sem_seg_labels": (H, W) int32,
+    # "sem_seg_score": (H, W) fp32} (the argmax map and its probability, without the volume)
+    cfg.MODEL.CATSEG_HIP.OUTPUT = "probs"
     return cfg

@@ -12,6 +12,8 @@ need the dispatcher); these are the registered surface for code that composes th
   catseg::attention        softmax attention, dense / causal / Swin window (catseg_attention)
   catseg::class_attention  fused norm1 + q/k/v + linear class attention (catseg_class_attention)
   catseg::postprocess      sigmoid + bilinear resize (catseg_postprocess; cat_seg_model.py:222-228)
+  catseg::postprocess_argmax  the same fused with the argmax over the classes -> (labels, score)
+                           (catseg_postprocess_argmax; + plain_train_net.py:107-116)
   catseg::linear           y = act(x W^T + b) with a registered backward (catseg_gemm forward,
                            catseg_gemm_ex / catseg_colsum backward): the training kernels through autograd
   catseg::head_logits      the whole eval forward of a registered CATSeg model up to the logits
@@ -118,6 +120,24 @@ def postprocess(logits: torch.Tensor, H: int, W: int, crop_h: int, crop_w: int) 
 @postprocess.register_fake
 def _(logits, H, W, crop_h, crop_w):
     return logits.new_empty((logits.shape[0], logits.shape[1], H, W), dtype=torch.float32)
+
+
+@torch.library.custom_op("catseg::postprocess_argmax", mutates_args=())
+def postprocess_argmax(logits: torch.Tensor, H: int, W: int, crop_h: int, crop_w: int,
+                       sigmoid: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """argmax and max over T of what catseg::postprocess (sigmoid) / the plain bilinear resize (not
+    sigmoid) computes: (B, T, h, w) fp32 -> labels (B, H, W) int32, score (B, H, W) fp32
+    (catseg_postprocess_argmax)."""
+    labels = torch.empty(logits.shape[0], H, W, device=logits.device, dtype=torch.int32)
+    score = torch.empty(logits.shape[0], H, W, device=logits.device, dtype=torch.float32)
+    ops.postprocess_argmax(logits.contiguous(), labels, score, crop=(crop_h, crop_w), sigmoid=sigmoid)
+    return labels, score
+
+
+@postprocess_argmax.register_fake
+def _(logits, H, W, crop_h, crop_w, sigmoid):
+    return (logits.new_empty((logits.shape[0], H, W), dtype=torch.int32),
+            logits.new_empty((logits.shape[0], H, W), dtype=torch.float32))
 
 
 # ------------------------------------------------------------------------------------- linear (+ backward)

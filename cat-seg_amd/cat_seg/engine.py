@@ -800,13 +800,21 @@ class CatSegEngine:
         ops.sliding_merge(logits, merged, kernel=k, stride=stride, out_res=res)
         return (merged, logits) if return_crops else merged
 
-    def forward_sliding(self, raw: torch.Tensor, sizes: torch.Tensor, out_hw) -> List[torch.Tensor]:
+    def forward_sliding(self, raw: torch.Tensor, sizes: torch.Tensor, out_hw, labels: bool = False) -> list:
         """Sliding-window probabilities resized to out_hw[n] = (height, width) per image
-        (sem_seg_postprocess of the 640² merge, cat_seg_model.py:215-217)."""
+        (sem_seg_postprocess of the 640² merge, cat_seg_model.py:215-217).  labels=True: per image the
+        (argmax map int32, its probability fp32) of that resize instead (catseg_postprocess_argmax without
+        the sigmoid, the 640 x 640 output included)."""
         merged = self.sliding_logits(raw, sizes)
         res = self.SLIDE_OUT
         outs = []
         for n, (H, W) in enumerate(out_hw):
+            if labels:
+                lab = torch.empty(1, H, W, device=self.device, dtype=torch.int32)
+                sc = torch.empty(1, H, W, device=self.device, dtype=_f32)
+                ops.postprocess_argmax(merged[n:n + 1], lab, sc, crop=(res, res), sigmoid=False)
+                outs.append((lab[0], sc[0]))
+                continue
             if (H, W) == (res, res):      # same-size bilinear (align_corners=False) is the identity
                 outs.append(merged[n])
                 continue

@@ -10,7 +10,8 @@ Mirrors the evaluators the reference registers (train_net.py:89-149):
   * `VOCbEvaluator`         — VOC with background: predictions >= 20 fold to 20
                               (train_net.py:43-67).
 `process()` bins every pixel with `catseg_semseg_confusion` (argmax over the class planes +
-int64 bincount, exact); `evaluate()` sums the matrices over ranks (torch.distributed, as
+int64 bincount, exact), or, for the `"sem_seg_labels"` outputs of MODEL.CATSEG_HIP.OUTPUT "labels",
+with `catseg_semseg_confusion_labels` from the argmax map the model already made; `evaluate()` sums the matrices over ranks (torch.distributed, as
 detectron2's `all_gather`, plain_train_net.py:136-146) and forms the metrics on the host
 from the small (N+1)^2 matrix.  With an `output_dir`, `process()` also keeps the COCO-stuff
 RLE records of every prediction (`encode_json_sem_seg`, plain_train_net.py:125,207-228; the RLE
@@ -195,6 +196,9 @@ class SemSegEvaluator:
 
     def _process(self, inputs, outputs):
         for inp, out in zip(inputs, outputs):
+            if isinstance(out, dict) and "sem_seg_labels" in out:
+                self._process_labels(inp, out["sem_seg_labels"])
+                continue
             probs = out["sem_seg"] if isinstance(out, dict) else out
             probs = probs.to(self._device, torch.float32).contiguous()
             gt = self._gt(inp)
@@ -209,6 +213,21 @@ class SemSegEvaluator:
                 if self.clamp_pred >= 0:
                     pred = pred.clamp(max=self.clamp_pred)
                 self._predictions.extend(self.encode_json_sem_seg(pred.cpu().numpy(), inp.get("file_name")))
+
+    def _process_labels(self, inp, labels):
+        """An output of MODEL.CATSEG_HIP.OUTPUT "labels": the argmax map is binned as it is
+        (catseg_semseg_confusion_labels), and is what the RLE records are built from."""
+        labels = labels.to(self._device, torch.int32).contiguous()
+        gt = self._gt(inp)
+        if labels.dim() != 2 or tuple(gt.shape) != tuple(labels.shape):
+            raise ValueError(f"gt {tuple(gt.shape)} vs label map {tuple(labels.shape)}")
+        ops.semseg_confusion_labels(labels, gt, self._conf, self._invalid, num_classes=self._num_classes,
+                                    ignore_label=self._ignore_label, clamp_pred=self.clamp_pred)
+        if self._output_dir:
+            pred = labels.to(torch.int64)
+            if self.clamp_pred >= 0:
+                pred = pred.clamp(max=self.clamp_pred)
+            self._predictions.extend(self.encode_json_sem_seg(pred.cpu().numpy(), inp.get("file_name")))
 
     def encode_json_sem_seg(self, sem_seg: np.ndarray, input_file_name) -> list:
         """COCO-stuff records of one argmax map (plain_train_net.py:207-228): one per label present,

@@ -541,6 +541,23 @@ def resize_bilinear(x, out, *, crop=None):
     return out
 
 
+def postprocess_argmax(logits, labels, score=None, *, crop=None, sigmoid=True):
+    """labels[b] = argmax over T of the sigmoid'ed (sigmoid=True, as `postprocess`) or plain (as
+    `resize_bilinear`) fp32 planes [B][T][h][w] cropped to `crop` and resized to labels' (H, W);
+    score[b] = that maximum (catseg_postprocess_argmax).  labels (B, H, W) int32, score (B, H, W)
+    fp32 or None; the (B, T, H, W) volume is never written."""
+    B, T, h, w = logits.shape
+    H, W = labels.shape[-2:]
+    ch, cw = crop if crop is not None else (h, w)
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == B * H * W
+    assert score is None or (score.dtype == torch.float32 and score.is_contiguous() and score.numel() == B * H * W)
+    with _rec("postprocess_argmax", 0, 4 * B * (T * ch * cw + H * W * (1 if score is None else 2))):
+        call("catseg_postprocess_argmax", logits.data_ptr(), B, T, h, w, ch, cw, 1 if sigmoid else 0,
+             labels.data_ptr(), 0 if score is None else score.data_ptr(), H, W, _stream())
+    return labels
+
+
 def avgpool_rows(x, out, *, S, H, W, C, pool):
     """nn.AvgPool2d(pool) over [S][H][W][C] rows -> out [S][H/ph][W/pw][C] (catseg_avgpool_rows)."""
     ph, pw = pool
@@ -740,5 +757,19 @@ def semseg_confusion(probs, gt, conf, n_invalid, *, num_classes, ignore_label=25
     assert conf.dtype == torch.int64 and conf.numel() == (num_classes + 1) ** 2 and n_invalid.dtype == torch.int64
     with _rec("semseg_confusion", 0, probs.numel() * 4 + gt.numel() * 4):
         call("catseg_semseg_confusion", probs.data_ptr(), T, H, W, gt.data_ptr(), num_classes, ignore_label,
+             clamp_pred, conf.data_ptr(), n_invalid.data_ptr(), _stream())
+    return conf
+
+
+def semseg_confusion_labels(labels, gt, conf, n_invalid, *, num_classes, ignore_label=255, clamp_pred=-1):
+    """conf += bincount((N+1) * labels' + gt') on the device (catseg_semseg_confusion_labels): the
+    binning of `semseg_confusion` from an argmax map.  labels, gt (H, W) int32, conf ((N+1)^2,) int64,
+    n_invalid (1,) int64."""
+    H, W = labels.shape
+    assert labels.is_contiguous() and labels.dtype == torch.int32
+    assert gt.is_contiguous() and gt.shape == (H, W) and gt.dtype == torch.int32
+    assert conf.dtype == torch.int64 and conf.numel() == (num_classes + 1) ** 2 and n_invalid.dtype == torch.int64
+    with _rec("semseg_confusion_labels", 0, labels.numel() * 4 + gt.numel() * 4):
+        call("catseg_semseg_confusion_labels", labels.data_ptr(), H, W, gt.data_ptr(), num_classes, ignore_label,
              clamp_pred, conf.data_ptr(), n_invalid.data_ptr(), _stream())
     return conf

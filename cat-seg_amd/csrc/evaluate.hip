@@ -48,6 +48,28 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
   atomicAdd(conf + n1 * arg + g, 1ull);
 }
 
+// The same binning from an int32 label map (catseg_postprocess_argmax's output) instead of the
+// probability volume: the clamp_pred fold, the ignore fold, 64-bit atomics, and n_invalid for a
+// ground-truth label or a prediction outside [0, num_classes] after the folds.
+__global__ __launch_bounds__(256) void confusion_labels_kernel(const int32_t* __restrict__ labels, int64_t HW,
+                                                               const int32_t* __restrict__ gt, int num_classes,
+                                                               int ignore_label, int clamp_pred,
+                                                               unsigned long long* __restrict__ conf,
+                                                               unsigned long long* __restrict__ n_invalid) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= HW) return;
+  int arg = labels[p];
+  if (clamp_pred >= 0 && arg >= clamp_pred) arg = clamp_pred;
+  int g = gt[p];
+  if (g == ignore_label) g = num_classes;
+  const int64_t n1 = (int64_t)num_classes + 1;
+  if (g < 0 || g > num_classes || arg < 0 || arg > num_classes) {
+    atomicAdd(n_invalid, 1ull);
+    return;
+  }
+  atomicAdd(conf + n1 * arg + g, 1ull);
+}
+
 // ---- training-branch loss (cat_seg_model.py:189-203): BCE-with-logits of the logits,
 // bilinearly upsampled (align_corners=False) to the target size, against one-hot targets
 // (ignore_value pixels: all-zero rows, still averaged), mean over B*H*W*T.  One block per
@@ -279,4 +301,20 @@ extern "C" int catseg_semseg_confusion(const float* probs, int64_t T, int64_t H,
                      num_classes, ignore_label, clamp_pred, (unsigned long long*)conf,
                      (unsigned long long*)n_invalid);
   return catseg_launch_status("semseg_confusion");
+}
+
+extern "C" int catseg_semseg_confusion_labels(const int32_t* labels, int64_t H, int64_t W, const int32_t* gt,
+                                              int num_classes, int ignore_label, int clamp_pred, int64_t* conf,
+                                              int64_t* n_invalid, void* stream) {
+  CATSEG_CHECK(labels && gt && conf && n_invalid, "semseg_confusion_labels: null pointer");
+  CATSEG_CHECK(H > 0 && W > 0 && num_classes > 0, "semseg_confusion_labels: empty shape");
+  CATSEG_CHECK(((uintptr_t)conf % 8) == 0 && ((uintptr_t)n_invalid % 8) == 0,
+               "semseg_confusion_labels: misaligned counters");
+  const int64_t HW = H * W;
+  const int64_t blocks = (HW + 255) / 256;
+  CATSEG_CHECK(blocks < ((int64_t)1 << 31), "semseg_confusion_labels: image too large");
+  hipLaunchKernelGGL(confusion_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, labels, HW,
+                     gt, num_classes, ignore_label, clamp_pred, (unsigned long long*)conf,
+                     (unsigned long long*)n_invalid);
+  return catseg_launch_status("semseg_confusion_labels");
 }

@@ -4,6 +4,7 @@
 #include <string.h>
 #include "common.h"
 #include "capi.h"
+#include "resize_idx.h"
 
 static thread_local char g_err[512] = "";
 
@@ -440,14 +441,7 @@ __global__ void fill_kernel(float* out, int64_t n, float v) {
 }
 
 // ---------------- preprocess + im2col --------------------------------------------
-// torch bilinear, align_corners=False: src = max(scale*(dst+0.5)-0.5, 0), scale = in/out
-DEV void lin_idx(int dst, int in_size, float scale, int& i0, int& i1, float& l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = fmaxf(src, 0.f);
-  i0 = (int)src;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
+// (the bilinear taps lin_idx: resize_idx.h)
 
 constexpr int PRE_NT = 256;
 

@@ -377,6 +377,19 @@ int catseg_postprocess(const float* logits, int64_t B, int T, int h, int w, int 
  * sem_seg_postprocess of the sliding branch (cat_seg_model.py:215-217). */
 int catseg_resize_bilinear(const float* in, int64_t B, int T, int h, int w, int crop_h, int crop_w,
                            float* out, int H, int W, void* stream);
+/* catseg_postprocess_argmax — the label map of the eval forward without the probability volume:
+ * replaces cat_seg_model.py:222-227 (sigmoid + sem_seg_postprocess) followed by the evaluator's
+ * argmax over the classes (plain_train_net.py:107-116).
+ * labels[b][y][x] = argmax_t v(b,t,y,x);  score[b][y][x] = max_t v(b,t,y,x)  (score may be NULL)
+ * v = the value catseg_postprocess (sigmoid != 0) / catseg_resize_bilinear (sigmoid == 0) computes
+ * on its banded path for the same (h, w, crop_h, crop_w, H, W).
+ * First maximum wins; NaN ranks above every number and the first NaN wins (torch.argmax; the rule
+ * and the bit test for NaN of confusion_kernel in evaluate.hip).
+ * logits fp32 [B][T][h][w]; labels int32 [B][H][W]; score fp32 [B][H][W].  The source patch of one
+ * 16 x 64 output tile (about (16 crop_h / H + 4) x (64 crop_w / W + 4) floats) must fit the 4096-float
+ * LDS stage: downsampling by more than ~3.5x per axis is rejected.  B <= 65535. */
+int catseg_postprocess_argmax(const float* logits, int64_t B, int T, int h, int w, int crop_h, int crop_w,
+                              int sigmoid, int32_t* labels, float* score, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------
  * catseg_swin_window_attention — fused LayerNorm(norm1) + [q|k|v] projection (+ the
@@ -496,6 +509,15 @@ int catseg_bce_onehot_loss_backward(const float* logits, int64_t B, int T, int h
 int catseg_semseg_confusion(const float* probs, int64_t T, int64_t H, int64_t W, const int32_t* gt,
                             int num_classes, int ignore_label, int clamp_pred, int64_t* conf,
                             int64_t* n_invalid, void* stream);
+
+/* catseg_semseg_confusion_labels — catseg_semseg_confusion from an int32 label map [H][W]
+ * (catseg_postprocess_argmax's output) instead of the probability volume: replaces the argmax of
+ * plain_train_net.py:107-116 applied to the output of cat_seg_model.py:222-227, which the label
+ * map already holds.  Same clamp_pred fold, ignore fold, int64 bins and n_invalid; a label outside
+ * [0, num_classes] after the clamp is counted in *n_invalid. */
+int catseg_semseg_confusion_labels(const int32_t* labels, int64_t H, int64_t W, const int32_t* gt,
+                                   int num_classes, int ignore_label, int clamp_pred, int64_t* conf,
+                                   int64_t* n_invalid, void* stream);
 
 #ifdef __cplusplus
 }
