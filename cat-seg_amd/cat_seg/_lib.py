@@ -303,6 +303,8 @@ _SIGS = {
     "catseg_conv2d_wgrad_workspace": [C.POINTER(Conv2dArgs)],
     "catseg_head_conv_backward": [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, i64, vp],
     "catseg_head_conv_backward_workspace": [i64, i32, i32, i32],
+    "catseg_vpt_rows_forward": [vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp],
+    "catseg_vpt_rows_backward": [vp, i64, vp, i64, i64, i32, i32, i32, i32, vp],
     "catseg_abi_version": [],
     "catseg_last_error": [],
 }

@@ -33,7 +33,7 @@ from .engine import CatSegEngine
 from .modeling.heads.cat_seg_head import CATSegHead  # noqa: F401  (registers the head)
 from .params import apply_clip_finetune, attach_parameters
 from .registry import META_ARCH_REGISTRY, build_sem_seg_head, configurable
-from .training import clip_image_train_forward, clip_text_train_forward, head_train_forward
+from .training import clip_image_train_forward, clip_text_train_forward, head_train_forward, vpt_strip_rows
 from .weights import CLIP as CLIP_PREFIX, synthesize_state_dict
 
 _DTYPES = {"bf16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32}
@@ -202,9 +202,10 @@ class CATSeg(nn.Module):
     @property
     def train_engine(self) -> CatSegEngine:
         """fp32 engine for the training step's CLIP encoders (the reference trains in fp32).  With CLIP
-        fine-tuning the autograd path reads the trained block weights from the parameters directly and
-        uses the engine only for the frozen embeddings, so it is rebuilt when a frozen CLIP weight changed
-        (a checkpoint load bumps its version), not after every optimizer step."""
+        fine-tuning the autograd path reads the trained block weights (and the visual prompt tokens) from
+        the parameters directly and uses the engine only for the frozen embeddings -- and, under
+        CLIP_FINETUNE "prompt", for the wholly frozen text encoder -- so it is rebuilt when a frozen CLIP
+        weight changed (a checkpoint load bumps its version), not after every optimizer step."""
         dev = self._engine_device()
         clip = self.sem_seg_head.predictor.clip_model
         trains = any(p.requires_grad for p in clip.parameters())
@@ -407,22 +408,36 @@ class CATSeg(nn.Module):
         the targets' size and BCE-with-logits against one-hot targets (ops.BCEOneHotLoss).
         Returns {"loss_sem_seg": 0-d tensor}; `loss.backward()` fills `.grad` of every Aggregator and
         upsampler parameter and of the CLIP parameters CLIP_FINETUNE trains (cat_seg_model.py:57-75:
-        'attention' = the q / v projections of both encoders' blocks): with any of those the CLIP
-        encoders run as autograd Functions too (cat_seg.training.clip_*_train_forward), else without
-        a graph on the engine."""
+        'attention' = the q / v projections of both encoders' blocks, 'prompt' = the visual prompt tokens,
+        'full' = every transformer parameter): an encoder with any of those runs as autograd Functions
+        too (cat_seg.training.clip_*_train_forward), else without a graph on the engine."""
         if self.device.type != "cuda":
             raise RuntimeError("CATSeg training runs on the GPU: move the model there first (model.to('cuda'))")
         eng = self.train_engine
         pred = self.sem_seg_head.predictor
         params = dict(self.named_parameters())
         raw, sizes_dev, _ = self._batch(eng, [x["image"] for x in batched_inputs])
-        if any(p.requires_grad for p in pred.clip_model.parameters()):
+        # each encoder runs as autograd Functions only when one of ITS OWN parameters trains (CLIP_FINETUNE
+        # "prompt" trains the visual prompt tokens alone: the text encoder is frozen, re-encoded every
+        # step on the engine as the reference does, without a graph)
+        vis = CLIP_PREFIX + "visual."
+        clip_named = [(k, p) for k, p in params.items() if k.startswith(CLIP_PREFIX)]
+        train_text = any(p.requires_grad for k, p in clip_named if not k.startswith(vis))
+        train_image = any(p.requires_grad for k, p in clip_named if k.startswith(vis))
+        if train_text:
             text = clip_text_train_forward(self.arch, params, eng, pred.class_tokens("train"))
-            feats, hooks = clip_image_train_forward(self.arch, params, eng, raw, sizes_dev)
         else:
             with torch.no_grad():
                 text = eng.encode_text(pred.class_tokens("train"))
+        if train_image:
+            feats, hooks = clip_image_train_forward(self.arch, params, eng, raw, sizes_dev)
+        else:
+            with torch.no_grad():
+                # the engine's rows carry the visual prompt rows (stride vision_seq_len): the head takes
+                # them without, as every reference block drops them from its output
                 feats, hooks = eng.encode_image(raw, sizes_dev)
+                feats = vpt_strip_rows(self.arch, feats)
+                hooks = [vpt_strip_rows(self.arch, h) for h in hooks]
         logits = head_train_forward(self.arch, params, feats, hooks, text)
         targets = torch.stack([x["sem_seg"].to(eng.device) for x in batched_inputs], dim=0)
         loss = ops.BCEOneHotLoss.apply(logits, targets, self.sem_seg_head.ignore_value)

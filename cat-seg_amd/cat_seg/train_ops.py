@@ -168,6 +168,55 @@ def add_dev_scalar(x, s):
     return x
 
 
+def _vpt_chk(t, rows, W):
+    assert t.dim() == 2 and t.shape == (rows, W) and t.stride(1) == 1, (tuple(t.shape), t.stride(), rows, W)
+
+
+def vpt_rows(dst, *, B, L0, P, src=None, prompt=None):
+    """The visual prompt rows of the vision stream (catseg_vpt_rows_forward).  dst (B*(L0+P), W) rows;
+    src (B*L0, W): dst's body rows = src, its tail rows = prompt (P, W) or zero when prompt is None;
+    src None: only the tail rows are rewritten, in place (the per-block writer)."""
+    _chk(dst, src, prompt)
+    W = dst.shape[1]
+    _vpt_chk(dst, B * (L0 + P), W)
+    if src is not None:
+        _vpt_chk(src, B * L0, W)
+    if prompt is not None:
+        _vpt_chk(prompt, P, W)
+    rows = B * ((L0 + P) if src is not None else P)
+    with _rec("vpt_rows_forward", 0, 8 * rows * W):
+        call("catseg_vpt_rows_forward", None if src is None else src.data_ptr(), 0 if src is None else src.stride(0),
+             None if prompt is None else prompt.data_ptr(), 0 if prompt is None else prompt.stride(0),
+             dst.data_ptr(), dst.stride(0), B, L0, P, W, 0, _stream())
+    return dst
+
+
+def vpt_strip(src, dst, *, B, L0, P):
+    """dst (B*L0, W) = the body rows of the stream src (B*(L0+P), W) (catseg_vpt_rows_forward, strip)."""
+    _chk(src, dst)
+    W = dst.shape[1]
+    _vpt_chk(src, B * (L0 + P), W)
+    _vpt_chk(dst, B * L0, W)
+    with _rec("vpt_rows_forward", 0, 8 * B * L0 * W):
+        call("catseg_vpt_rows_forward", src.data_ptr(), src.stride(0), None, 0, dst.data_ptr(), dst.stride(0), B, L0,
+             P, W, 1, _stream())
+    return dst
+
+
+def vpt_rows_backward(dx, dprompt, *, B, L0, P, beta=0):
+    """dprompt (P, W) (+)= the batch sum of dx's tail rows in the order b = 0..B-1, then those rows of dx
+    (B*(L0+P), W) zeroed, in one launch (catseg_vpt_rows_backward); dprompt None: zeroed only."""
+    _chk(dx, dprompt)
+    W = dx.shape[1]
+    _vpt_chk(dx, B * (L0 + P), W)
+    if dprompt is not None:
+        _vpt_chk(dprompt, P, W)
+    with _rec("vpt_rows_backward", 0, 8 * B * P * W):
+        call("catseg_vpt_rows_backward", dx.data_ptr(), dx.stride(0), None if dprompt is None else dprompt.data_ptr(),
+             0 if dprompt is None else dprompt.stride(0), B, L0, P, W, int(beta), _stream())
+    return dprompt
+
+
 def sum_classes(x, out, *, B, T, HW, C_, beta=0):
     """out[b*HW + p] (+)= sum_t x[(b*T + t)*HW + p] over the first C_ columns (catseg_sum_classes)."""
     _chk(x, out)

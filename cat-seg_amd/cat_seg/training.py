@@ -897,27 +897,99 @@ def _clip_block_params(P, p):
                                "mlp.c_proj.weight", "mlp.c_proj.bias")]
 
 
+class VptRowsFn(torch.autograd.Function):
+    """Transformer.forward's prompt insert before block i (model_vpt.py:258-259), the prompt rows at the
+    END of each image's sequence (CatSegEngine.vision_seq_len): x is either the (B*L0, W) body rows (block
+    0: expanded into a new (B*Ls, W) stream) or the (B*Ls, W) stream itself, whose tail rows are rewritten
+    in place (the previous block's outputs there are what the reference drops, model_vpt.py:215-216).
+    Backward: dprompt = the batch sum of the tail rows of the stream's gradient (the reference's repeat
+    over the batch), and those rows zeroed in what flows on: the overwritten outputs receive nothing."""
+
+    @staticmethod
+    def forward(ctx, x, prompt, B, L0):
+        P, W = prompt.shape
+        pr = prompt.detach().contiguous()
+        ctx.geo = (B, L0, P)
+        ctx.expand = x.shape[0] == B * L0
+        if ctx.expand:
+            out = _empty(B * (L0 + P), W, like=x)
+            return TO.vpt_rows(out, B=B, L0=L0, P=P, src=x.contiguous(), prompt=pr)
+        assert x.is_contiguous() and x.shape[0] == B * (L0 + P)
+        ctx.mark_dirty(x)
+        return TO.vpt_rows(x, B=B, L0=L0, P=P, prompt=pr)
+
+    @staticmethod
+    def backward(ctx, dx):
+        B, L0, P = ctx.geo
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = dx.contiguous()
+        dprompt = _empty(P, dx.shape[1], like=dx) if need_p else None
+        if need_p or (need_x and not ctx.expand):
+            TO.vpt_rows_backward(dx, dprompt, B=B, L0=L0, P=P)
+        if not need_x:
+            return None, dprompt, None, None
+        if ctx.expand:
+            return TO.vpt_strip(dx, _empty(B * L0, dx.shape[1], like=dx), B=B, L0=L0, P=P), dprompt, None, None
+        return dx, dprompt, None, None
+
+
+class VptStripFn(torch.autograd.Function):
+    """The blocks' prompt drop (model_vpt.py:215-216, 238-239) where the body rows alone are read (the
+    forward hooks, the dense block): (B*Ls, W) stream -> (B*L0, W).  Backward: zero tail rows."""
+
+    @staticmethod
+    def forward(ctx, x, B, L0, P):
+        ctx.geo = (B, L0, P)
+        return TO.vpt_strip(x.contiguous(), _empty(B * L0, x.shape[1], like=x), B=B, L0=L0, P=P)
+
+    @staticmethod
+    def backward(ctx, d):
+        B, L0, P = ctx.geo
+        out = _empty(B * (L0 + P), d.shape[1], like=d)
+        return TO.vpt_rows(out, B=B, L0=L0, P=P, src=d.contiguous()), None, None, None
+
+
+def vpt_strip_rows(arch: CatSegArch, x: torch.Tensor) -> torch.Tensor:
+    """The body rows (B*(1+G^2), C) of prompt-carrying rows (B*(1+G^2+P), C) as the engine's image
+    encoder returns them; x itself without visual prompt tuning.  No graph."""
+    if not arch.vpt:
+        return x
+    L0 = arch.grid * arch.grid + 1
+    B = x.shape[0] // (L0 + arch.vpt)
+    return TO.vpt_strip(x.contiguous(), _empty(B * L0, x.shape[1], like=x), B=B, L0=L0, P=arch.vpt)
+
+
 def clip_image_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], eng, raw: torch.Tensor,
                              sizes: torch.Tensor):
     """CLIP.encode_image(dense=True) with the forward hooks (cat_seg_model.py:84-87,144-146,
     model_vpt.py:288-314), the transformer blocks as autograd Functions.  The embedding (patch conv,
     class / positional embedding, ln_pre) is outside `transformer` and frozen under every CLIP_FINETUNE
     mode (cat_seg_model.py:58-75): the engine computes it without a graph.
+    With visual prompt tuning (model_vpt.py:243-266) the stream carries PROMPT_LENGTH prompt rows behind
+    each image's tokens: block i < PROMPT_DEPTH runs on prompt_tokens[i] there (VptRowsFn), the hooks and
+    the last (dense) block read the stripped rows (VptStripFn) -- the dense block is row-wise plus the CLS
+    row and its prompt rows are dropped, so they reach nothing and prompt_tokens[layers - 1] gets a zero
+    gradient, as in the reference.
     Returns feats [B*(1+G^2)][C_o] and the two hook outputs [B*(1+G^2)][W]."""
     from .weights import CLIP
-    if arch.vpt:
-        raise NotImplementedError("training step: visual prompt tuning (CLIP_FINETUNE 'prompt') is not built")
     B = raw.shape[0]
-    L_ = arch.grid * arch.grid + 1
+    L0 = arch.grid * arch.grid + 1
+    Np = arch.vpt                    # PROMPT_DEPTH below the layer count: CatSegEngine refuses it
+    L_ = L0 + Np
     x = eng.embed_image(raw, sizes)
     p = CLIP + "visual."
+    prompts = P[p + "transformer.prompt_tokens"] if Np else None
     hooks: List[torch.Tensor] = []
     for i in range(arch.vision_layers - 1):
+        if Np:
+            x = VptRowsFn.apply(x, prompts[i], B, L0)
         x = ClipBlockFn.apply(x, (B, L_, arch.vision_heads, False),
                               *_clip_block_params(P, f"{p}transformer.resblocks.{i}."))
         if i in arch.hook_layers:
-            hooks.append(x)
-    x = ClipDenseBlockFn.apply(x, (B, L_), *_clip_block_params(P, f"{p}transformer.resblocks.{arch.vision_layers - 1}."))
+            hooks.append(VptStripFn.apply(x, B, L0, Np) if Np else x)
+    if Np:
+        x = VptStripFn.apply(x, B, L0, Np)
+    x = ClipDenseBlockFn.apply(x, (B, L0), *_clip_block_params(P, f"{p}transformer.resblocks.{arch.vision_layers - 1}."))
     feats = LnProjFn.apply(x, P[p + "ln_post.weight"], P[p + "ln_post.bias"], P[p + "proj"])
     return feats, hooks
 
@@ -947,11 +1019,9 @@ def head_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], feats: torc
     """Training-mode head (cat_seg_model.py:178-188 -> CATSegHead.forward -> Aggregator.forward,
     model.py:683-725), fp32, with the HIP backward.  P: parameters by reference key (nn.Parameters
     of the model); feats [B*(1+G^2)][C_o] dense CLIP tokens, hooks 2 x [B*(1+G^2)][W_v] (the forward
-    hooks of cat_seg_model.py:84-87), text [T][C_o] class embeddings.  Returns logits [B][T][4G][4G]."""
+    hooks of cat_seg_model.py:84-87; with visual prompt tuning both without the prompt rows, which every
+    block drops from its output, model_vpt.py:215-216), text [T][C_o] class embeddings.  Returns logits [B][T][4G][4G]."""
     a = arch
-    if a.vpt:
-        raise NotImplementedError("training step: visual prompt tuning is not built (frozen-CLIP features "
-                                  "carry the prompt rows)")
     if a.attention_type not in ("linear", "full"):
         raise NotImplementedError(f"training step: unknown ATTENTION_TYPE {a.attention_type!r}")
     G = a.grid

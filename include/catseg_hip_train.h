@@ -130,6 +130,32 @@ int catseg_convt_gather(const float* dout, int64_t ld, int64_t S, int hin, int w
                         void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Visual prompt tuning (CLIP_FINETUNE "prompt"): the prompt rows of the vision residual stream.
+ * Image b of the stream holds L0 = 1 + grid^2 body rows (CLS + patch tokens) at rows b*Ls .. and its
+ * P prompt rows behind them, at rows b*Ls + L0 .. b*Ls + Ls - 1, Ls = L0 + P (the reference puts them
+ * after CLS; attention is order-free over keys).  W % 4 == 0, every pointer 16-byte aligned, every
+ * leading dimension % 4 == 0 and >= W.
+ * ------------------------------------------------------------------------- */
+/* catseg_vpt_rows_forward — Transformer.forward's prompt insert (model_vpt.py:258-259) and the blocks'
+ * prompt drop (model_vpt.py:215-216, 238-239) as row copies:
+ *   strip == 0, src != NULL   dst (B*Ls rows) = the body rows of src (B*L0 rows) with prompt [P][W]
+ *                             (one layer's prompt_tokens[i]) in every image's tail rows; prompt == NULL
+ *                             writes zero tails (the backward of the strip)
+ *   strip == 0, src == NULL   only the tail rows of dst are rewritten, in place: the per-block writer
+ *   strip != 0                dst (B*L0 rows) = the body rows of src (B*Ls rows); prompt must be NULL
+ * The row spans of src / prompt must not overlap dst's. */
+int catseg_vpt_rows_forward(const float* src, int64_t ld_src, const float* prompt, int64_t ld_prompt, float* dst,
+                            int64_t ld_dst, int64_t B, int L0, int P, int W, int strip, void* stream);
+/* catseg_vpt_rows_backward — the gradient of the insert (model_vpt.py:259: prompt_tokens[i] repeated
+ * over the batch) and of the previous block's drop (model_vpt.py:215-216), one launch: dx the gradient of
+ * a block's input stream (B*Ls rows); dprompt[p] = beta * dprompt[p] + sum_b dx[b*Ls + L0 + p], summed
+ * in the fixed order b = 0..B-1 by one thread per element (no atomics: bit-reproducible); then those
+ * rows of dx are set to zero, so what flows on to the previous block carries no gradient for the tail
+ * outputs the writer overwrote.  dprompt == NULL (frozen prompts): the rows are zeroed only. */
+int catseg_vpt_rows_backward(float* dx, int64_t ld_dx, float* dprompt, int64_t ld_dprompt, int64_t B, int L0, int P,
+                             int W, int beta, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Attention backward
  * ------------------------------------------------------------------------- */
 /* catseg_window_attention_backward — WindowAttention backward (model.py:86-114, shift / -100 region mask

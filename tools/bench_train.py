@@ -1,7 +1,8 @@
 """Training-step throughput of the MI355X path (not the headline metric).
 
 One step = the reference Trainer's iteration (train_net.py:298-311 via detectron2 SimpleTrainer):
-CATSeg training forward (fp32 CLIP with CLIP_FINETUNE "attention", the aggregation head) -> BCE loss
+CATSeg training forward (fp32 CLIP with CLIP_FINETUNE "attention" by default -- --clip-finetune and
+--prompt-length select the other modes and visual prompt tuning --, the aggregation head) -> BCE loss
 -> backward through the HIP kernels -> AdamW with full-model clipping (train_net.py:228-253),
 on the reference training config (configs/vitb_384.yaml: ViT-B/16 @384, COCO-Stuff's 171 classes,
 POOLING [2,2], IMS_PER_BATCH 4, BASE_LR 2e-4, CLIP_GRADIENTS full_model 0.01), synthetic images and
@@ -21,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "cat-seg_amd"), ROOT]
 
 from cat_seg import add_cat_seg_config, build_model, get_cfg, ops  # noqa: E402
+from cat_seg.arch import PRESETS  # noqa: E402
 from cat_seg.optim import build_optimizer  # noqa: E402
 
 
@@ -31,7 +33,11 @@ def main():
     ap.add_argument("--classes", type=int, default=171)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--finetune", default="attention", choices=["attention", "none", "full"])
+    ap.add_argument("--clip-finetune", "--finetune", dest="finetune", default="attention",
+                    choices=["attention", "prompt", "full", "none"],
+                    help="MODEL.SEM_SEG_HEAD.CLIP_FINETUNE (cat_seg_model.py:57-75)")
+    ap.add_argument("--prompt-length", type=int, default=0,
+                    help="visual prompt tokens per vision block (PROMPT_LENGTH; PROMPT_DEPTH = the layer count)")
     ap.add_argument("--attention-type", default="linear", choices=["linear", "full"],
                     help="MODEL.SEM_SEG_HEAD.ATTENTION_TYPE of the class aggregation (model.py:331-334)")
     ap.add_argument("--profile", action="store_true")
@@ -51,7 +57,12 @@ def main():
     if a.clip != "ViT-B/16":
         cfg.merge_from_list(["MODEL.SEM_SEG_HEAD.TEXT_GUIDANCE_DIM", "768",
                              "MODEL.SEM_SEG_HEAD.APPEARANCE_GUIDANCE_DIM", "768"])
+    if a.prompt_length > 0:
+        layers = PRESETS[a.clip].vision_layers
+        cfg.merge_from_list(["MODEL.SEM_SEG_HEAD.PROMPT_DEPTH", str(layers),
+                             "MODEL.SEM_SEG_HEAD.PROMPT_LENGTH", str(a.prompt_length)])
     model = build_model(cfg).cuda().train()
+    assert model.arch.prompt_depth in (0, model.arch.vision_layers)
     toks = np.load(os.path.join(ROOT, "tests", "golden", "class_tokens.npz"))["ade847"][:a.classes]
     model.sem_seg_head.predictor.set_class_tokens(torch.from_numpy(toks.astype(np.int64)))
     opt = build_optimizer(cfg, model)
@@ -83,7 +94,7 @@ def main():
            "loss": float(loss.detach()), "grad_norm": float(opt.last_grad_norm[0]),
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
            "config": {"clip": a.clip, "resolution": S, "clip_resolution": model.clip_resolution[0], "classes": a.classes, "batch": a.batch, "pooling": [2, 2],
-                      "clip_finetune": a.finetune, "attention_type": a.attention_type, "optimizer": "AdamW (HIP) + full-model clip 0.01"}}
+                      "clip_finetune": a.finetune, "prompt_length": a.prompt_length, "attention_type": a.attention_type, "optimizer": "AdamW (HIP) + full-model clip 0.01"}}
     if a.profile:
         ops.PROFILE = []
         step()
