@@ -571,7 +571,7 @@ template <int NW, int QT, bool L2S = false>
 void launch_vit3(const AttnP& p, hipStream_t st) {
   dim3 grid((unsigned)((p.L + 16 * NW * QT - 1) / (16 * NW * QT)), (unsigned)(p.n_seq * p.H));
   // write-through only when every byte offset of the output fits its 31-bit offset
-  const bool wt = g_attn_store && wt_fits((int64_t)p.n_seq * p.L * p.ldo, 2);
+  const bool wt = g_attn_store && fits_31bit((int64_t)p.n_seq * p.L * p.ldo, 2);
   g_attn_last_wt = wt;
   if (wt) hipLaunchKernelGGL((vit_attn3_kernel<NW, QT, L2S, true>), grid, dim3(NW * 64), 0, st, p);
   else hipLaunchKernelGGL((vit_attn3_kernel<NW, QT, L2S>), grid, dim3(NW * 64), 0, st, p);

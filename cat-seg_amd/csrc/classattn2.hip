@@ -388,7 +388,7 @@ extern "C" int catseg_class_attention(const CatsegClassAttnArgs* a, void* stream
   p.y = (bf16*)a->y; p.ld_y = a->ld_y;
   p.B = a->B; p.T = a->T; p.HW = a->HW;
   p.dbg = g_classattn_variant >= 16 ? g_classattn_variant - 16 : 0;
-  p.wt = g_cls_store && a->B * a->T * (int64_t)a->HW * a->ld_y * 2 < 0x7fffffffLL;
+  p.wt = g_cls_store && fits_31bit(a->B * a->T * (int64_t)a->HW * a->ld_y, 2);
   const int cus = catseg_device_cus();
   const int64_t npix = a->B * a->HW;
   const unsigned grid = (unsigned)std::min<int64_t>(npix, 2LL * cus);

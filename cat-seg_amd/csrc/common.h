@@ -65,9 +65,10 @@ DEV void st8_wt(void* base, int64_t byte_off, uint2 v) {
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, 0x7fffffff, 0x00020000);
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i32_t, v), r, (int)byte_off, 0, 16);
 }
-// host side of the above: a launch may pick a write-through store form only when every byte offset of
-// its output (out_elems elements of elem_bytes each, from the base pointer) fits the 31-bit offset
-inline bool wt_fits(int64_t out_elems, int64_t elem_bytes) { return out_elems * elem_bytes < 0x7fffffffLL; }
+// host side of the above, and of every other 32-bit byte offset from a base pointer (buffer loads): a
+// launch may pick such a form only when every byte offset of the operand (elems elements of elem_bytes
+// each) fits 31 bits
+inline bool fits_31bit(int64_t elems, int64_t elem_bytes) { return elems * elem_bytes < 0x7fffffffLL; }
 
 // load 4 consecutive elements as floats
 template <typename T> DEV void load4(const T* p, float out[4]);

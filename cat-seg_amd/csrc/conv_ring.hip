@@ -818,7 +818,7 @@ int catseg_conv3x3_ring(const CatsegConvArgs* a, hipStream_t st) {
   p.gmean = a->gn_mean; p.grstd = a->gn_rstd; p.ggamma = a->gn_gamma; p.gbeta = a->gn_beta; p.gcpg = a->gn_cpg;
   p.add = a->addend; p.add_ss = a->addend_slice_stride; p.add_div = a->addend_div > 0 ? a->addend_div : 1;
   p.out = (bf16*)a->out; p.stats = a->stats;
-  p.wt = g_ring_store && (int64_t)a->S * a->H * a->W * a->c_out * 2 < 0x7fffffffLL;
+  p.wt = g_ring_store && fits_31bit((int64_t)a->S * a->H * a->W * a->c_out, 2);
   // weights in registers: 9 taps x C/16 half-steps x COUT/WCO/16 fragments
   switch (v) {
     case 1: return launch_ring<64, 32, 4, 1, 156>(p, st);
@@ -955,7 +955,7 @@ extern "C" int catseg_upconv3x3(const CatsegConvArgs* a, void* stream) {
   p.gmean = a->gn_mean; p.grstd = a->gn_rstd; p.ggamma = a->gn_gamma; p.gbeta = a->gn_beta; p.gcpg = a->gn_cpg;
   p.add = a->addend; p.add_ss = a->addend_slice_stride; p.add_div = a->addend_div > 0 ? a->addend_div : 1;
   p.out = (bf16*)a->out; p.stats = a->stats;
-  p.wt = g_ring_store && (int64_t)a->S * a->H * a->W * a->c_out * 2 < 0x7fffffffLL;
+  p.wt = g_ring_store && fits_31bit((int64_t)a->S * a->H * a->W * a->c_out, 2);
   p.up_split = 1;
   hipStream_t st = (hipStream_t)stream;
   // 64-pixel chunks (a 48-wide chunk spans <= 3 rows: 5-row ring, <= 2 new rows = 104 positions):

@@ -38,7 +38,16 @@ struct EpiArgs {
   void* out; int64_t ldo;
   int store_mode; int cvt_k, cvt_hin, cvt_win, cvt_cout;
   const float* sa; const float* sw;   // fp8 path: per-row scales of A and W (dequant in the epilogue)
-  int pf;                             // gemm3 lean epilogue: next round's residual in flight (g_epi_prefetch)
+  int pf;                             // epilogue / store forms of the gemm3 and gemm6 kernels: EpiForm bits (epi_forms)
+};
+// EpiArgs::pf.  The two write-through forms carry a 31-bit byte offset: epi_forms clears them for larger outputs.
+enum EpiForm : int {
+  EF_PREFETCH = 1,   // gemm3 lean epilogue: next round's residual in flight, bias loaded once (knob epi_prefetch)
+  EF_WIDE_REG = 2,   // gemm6 bf16 outputs: register-side epilogue wide_epilogue_bf16 (wide_epi)
+  EF_WIDE_NT = 4,    // wide_epilogue_bf16 stores: nt (wide_store 1)
+  EF_WIDE_WT = 8,    //                            sc1 write-through (wide_store 2)
+  EF_G3_NT = 16,     // gemm3 lean fp32 stores: nt (gemm3_store 1)
+  EF_G3_WT = 32,     //                         sc1 write-through (gemm3_store 2)
 };
 
 template <typename TO>
@@ -613,7 +622,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm3_kernel(const bf16* __res
   constexpr int IPT = Lean::IPT;
   constexpr bool ONE = Lean::ONE;
   if constexpr (ONE) {
-    if (e.pf & 1) {
+    if (e.pf & EF_PREFETCH) {
       const int c8 = (tid % (BN / 8)) * 8;
       const int64_t n = n0 + c8;
       float b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -674,13 +683,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm3_kernel(const bf16* __res
               for (int r = 0; r < 8; ++r) v[r] += rc[k][r];
             }
             if constexpr (sizeof(TO) == 4) {
-              if (e.pf & 16) {          // A/B knob gemm3_store 1: nt stores of the fp32 rows
+              if (e.pf & EF_G3_NT) {    // A/B knob gemm3_store 1: nt stores of the fp32 rows
                 float* p = reinterpret_cast<float*>(e.out) + m * e.ldo + n;
                 __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
                 __builtin_nontemporal_store(f32x4{v[4], v[5], v[6], v[7]}, reinterpret_cast<f32x4*>(p + 4));
                 continue;
               }
-              if (e.pf & 32) {          // gemm3_store 2: sc1 write-through
+              if (e.pf & EF_G3_WT) {    // gemm3_store 2: sc1 write-through
                 const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(e.out, (short)0, 0x7fffffff, 0x00020000);
                 const int off = (int)((m * e.ldo + n) * 4);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, f32x4{v[0], v[1], v[2], v[3]}), r, off, 0, 16);
@@ -894,8 +903,8 @@ DEV void wide_epilogue_bf16(const EpiArgs& e, f32x4 (&acc)[FN][FM], bf16* smem, 
     for (int k = 0; k < IPT; ++k)
       if (tid + k * NT4 < ITEMS && mr[k] < M) {
         bf16* p = reinterpret_cast<bf16*>(e.out) + mr[k] * e.ldo + n0 + cc[k];
-        if (e.pf & 4) __builtin_nontemporal_store(__builtin_bit_cast(i32x4, val[k]), reinterpret_cast<i32x4*>(p));
-        else if (e.pf & 8) {
+        if (e.pf & EF_WIDE_NT) __builtin_nontemporal_store(__builtin_bit_cast(i32x4, val[k]), reinterpret_cast<i32x4*>(p));
+        else if (e.pf & EF_WIDE_WT) {
           const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(e.out, (short)0, 0x7fffffff, 0x00020000);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, val[k]), r,
                                                  (int)((mr[k] * e.ldo + n0 + cc[k]) * 2), 0, 16);   // sc1 write-through
@@ -903,6 +912,17 @@ DEV void wide_epilogue_bf16(const EpiArgs& e, f32x4 (&acc)[FN][FM], bf16* smem, 
       }
   }
 }
+
+// gemm6's choice of the register-side bf16 epilogue (wide_epilogue_bf16, the only gemm6 path with the
+// wide_store forms): the kernel's own condition, shared with launch6 so that gemm_last_wt reports what the
+// kernel does.  CAN is the compile-time half (bf16 output, an even count of m-fragments), GEMM6_REG_USE the
+// run-time half: a macro, because behind a bool-returning function the same expression compiles to other
+// branches, and with them another register allocation, in the EPI 1 kernels.
+template <typename TO, int BM>
+struct Gemm6Reg {
+  static constexpr bool CAN = sizeof(TO) == 2 && (BM / 32) % 2 == 0;
+};
+#define GEMM6_REG_USE(EPI, e) (((e).pf & EF_WIDE_REG) && !((EPI) == 1 && (e).res))
 
 // gemm6: the wide tile as a PING-PONG loop (cdna_hip_programming.md §5, the staggered 8-wave
 // template) with FULL-LINE staging.  Waves w and w + 4 share a SIMD; the waves of the second m-half
@@ -920,7 +940,7 @@ DEV void wide_epilogue_bf16(const EpiArgs& e, f32x4 (&acc)[FN][FM], bf16* smem, 
 //   tile t + 1 is read from @4t+4 (group 0) / @4t+5 (group 1), so every wave waits its own DMA of
 //   t + 1 before the barrier closing @4t+3: group 0 at the end of C(t,1), group 1 at the end of L(t,1).
 // Swizzle: the 16-byte chunk c of row r sits at slot c ^ ((r / 2) % 8) (Swz<64>, as gemm3).
-template <typename TO, int BM, int BN, int EPI, int ABL = 0>
+template <typename TO, int BM, int BN, int EPI>
 __global__ __launch_bounds__(512) void gemm6_kernel(const bf16* __restrict__ A, int64_t lda, const bf16* __restrict__ W,
                                                     int64_t ldw, int64_t M, int64_t K, int tiles_n, EpiArgs e,
                                                     int group_m) {
@@ -997,42 +1017,29 @@ __global__ __launch_bounds__(512) void gemm6_kernel(const bf16* __restrict__ A, 
       for (int i = 0; i < FN; ++i) afrag[i] = *fptr(Ws, wn + 16 * i, h);
 #pragma unroll
       for (int j = 0; j < FM; ++j) bfrag[j] = *fptr(As, wm + 16 * j, h);
-      if (ABL != 1 && h == 0 && kt + 1 < ktiles) issue(kt + 1);
+      if (h == 0 && kt + 1 < ktiles) issue(kt + 1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (ABL != 1 && h == 1 && grp == 1) wait_vmcnt<0>();     // group 1: own DMA of kt + 1 landed
+      if (h == 1 && grp == 1) wait_vmcnt<0>();     // group 1: own DMA of kt + 1 landed
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       // ---- COMPUTE(kt, h) ----
       __builtin_amdgcn_s_setprio(1);
-      if constexpr (ABL == 2) {
 #pragma unroll
-        for (int j = 0; j < FM; ++j) asm volatile("" :: "v"(bfrag[j]));
+      for (int j = 0; j < FM; ++j)
 #pragma unroll
-        for (int i = 0; i < FN; ++i) asm volatile("" :: "v"(afrag[i]));
-      } else {
-#pragma unroll
-        for (int j = 0; j < FM; ++j)
-#pragma unroll
-          for (int i = 0; i < FN; ++i) acc[i][j] = mfma_bf16(afrag[i], bfrag[j], acc[i][j]);
-      }
+        for (int i = 0; i < FN; ++i) acc[i][j] = mfma_bf16(afrag[i], bfrag[j], acc[i][j]);
       __builtin_amdgcn_s_setprio(0);
-      if (ABL != 1 && h == 1 && grp == 0) wait_vmcnt<0>();     // group 0: own DMA of kt + 1 landed
+      if (h == 1 && grp == 0) wait_vmcnt<0>();     // group 0: own DMA of kt + 1 landed
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
     }
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();          // re-align the groups' barrier counts
-  if constexpr (ABL == 3) {   // ablation: no epilogue (the accumulators kept live)
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-      for (int j = 0; j < FM; ++j) asm volatile("" :: "v"(acc[i][j]));
-    return;
-  }
-  if constexpr (sizeof(TO) == 2 && FM % 2 == 0) {
-    if ((e.pf & 2) && !(EPI == 1 && e.res)) {
+  static_assert(FM == BM / 32, "Gemm6Reg mirrors the m-fragment count");
+  if constexpr (Gemm6Reg<TO, BM>::CAN) {
+    if (GEMM6_REG_USE(EPI, e)) {
       wide_epilogue_bf16<BM, BN, EPI, FM, FN>(e, acc, smem, M, m0, n0);
       return;
     }
@@ -1040,83 +1047,169 @@ __global__ __launch_bounds__(512) void gemm6_kernel(const bf16* __restrict__ A, 
   wide_epilogue<TO, BM, BN, EPI, FM, FN>(e, acc, smem, M, m0, n0);
 }
 
-int g_gemm_group = 4;   // gemm3 tile order: 0 = row-major, G > 0 = G m-tiles per group (catseg_set_gemm_group); 4 measured best (fc2 48.6 -> 47.4 us)
+// ------------------------------------------------------------------------------------
+// Host side: argument conversion, the tile table, dispatch.
+// ------------------------------------------------------------------------------------
+int g_gemm_group = 4;    // gemm3 tile order: 0 = row-major, G > 0 = G m-tiles per group (catseg_set_gemm_group); 4 measured best (fc2 48.6 -> 47.4 us)
+int g_gemm4_group = 5;   // gemm6 tile order: G m-tiles per group (catseg_set_gemm4_group)
+int g_gemm_wide = 1;     // 1 = the automatic choice includes the wide ping-pong tiles (gemm6); 0 = round-5 candidates
+int g_gemm_variant = 0;  // 0 = automatic; >0 forces the bf16 tile of TILES with that id (tests / tuning)
+int g_gemm_f8_variant = 0;   // the same for the fp8 tiles
 
-// out_bytes = sizeof(TO): the write-through store forms (pf bits 8 / 32) carry a 31-bit byte offset, so
-// an output whose extent does not fit falls to the kernels' plain-store branch
-EpiArgs make_epi(const CatsegGemmArgs* g, int out_bytes) {
+RowMap to_rowmap(const CatsegRowMap& m) { return RowMap{m.d1, m.m1, m.s1, m.d2, m.m2, m.s2, m.off}; }
+// the map reads row m for every m < M (the kernels' own test, gemm3_kernel `ident`)
+bool is_identity(const CatsegRowMap& m, int64_t M) { return m.d1 == 1 && m.m1 >= M && m.s1 == 1 && m.m2 == 1 && m.off == 0; }
+
+// The kernels' view of the epilogue arguments.  pf: the gemm3 / gemm6 launchers pass epi_forms(); gemm_kernel and
+// gemm2_kernel (epilogue4) read no form flag.  The fp8 launcher adds its scales.
+EpiArgs make_epi(const CatsegGemmArgs* g, int pf = 0) {
   EpiArgs e;
   e.bias = g->bias;
-  e.add = g->add; e.ld_add = g->ld_add; e.add_ncols = g->add_ncols;
-  e.addmap = RowMap{g->addmap.d1, g->addmap.m1, g->addmap.s1, g->addmap.d2, g->addmap.m2, g->addmap.s2, g->addmap.off};
+  e.add = g->add; e.ld_add = g->ld_add; e.addmap = to_rowmap(g->addmap); e.add_ncols = g->add_ncols;
   e.act = g->act; e.alpha = g->alpha;
   e.res = g->res; e.ld_res = g->ld_res; e.res2 = g->res2; e.ld_res2 = g->ld_res2;
   e.out = g->out; e.ldo = g->ldo;
   e.store_mode = g->store_mode; e.cvt_k = g->cvt_k; e.cvt_hin = g->cvt_hin; e.cvt_win = g->cvt_win;
   e.cvt_cout = g->cvt_cout;
   e.sa = nullptr; e.sw = nullptr;
-  e.pf = g_epi_prefetch | (g_wide_epi ? 2 : 0) | (g_wide_store == 1 ? 4 : g_wide_store == 2 ? 8 : 0) |
-         (g_gemm3_store == 1 ? 16 : g_gemm3_store == 2 ? 32 : 0);
-  const int64_t out_elems = g->store_mode == 0 ? g->M * g->ldo : g->M * g->N;   // scatter: M x k x k x cout, dense
-  if (!wt_fits(out_elems, out_bytes)) e.pf &= ~(8 | 32);
+  e.pf = pf;
   return e;
 }
 
-int g_gemm4_group = 5;   // gemm6 tile order: G m-tiles per group (catseg_set_gemm4_group)
+// EpiArgs::pf from the knobs.  out_bytes = sizeof(TO): an output whose extent does not fit the write-through
+// forms' 31-bit byte offset falls to the kernels' plain-store branch
+int epi_forms(const CatsegGemmArgs* g, int out_bytes) {
+  int pf = (g_epi_prefetch ? EF_PREFETCH : 0) | (g_wide_epi ? EF_WIDE_REG : 0) |
+           (g_wide_store == 1 ? EF_WIDE_NT : g_wide_store == 2 ? EF_WIDE_WT : 0) |
+           (g_gemm3_store == 1 ? EF_G3_NT : g_gemm3_store == 2 ? EF_G3_WT : 0);
+  const int64_t out_elems = g->store_mode == 0 ? g->M * g->ldo : g->M * g->N;   // scatter: M x k x k x cout, dense
+  if (!fits_31bit(out_elems, out_bytes)) pf &= ~(EF_WIDE_WT | EF_G3_WT);
+  return pf;
+}
 
-// the wide ping-pong tiles (gemm6); ABL > 0: timing ablations (tools/micro_gemm.py 56-60, wrong outputs)
-template <typename TO, int BM, int BN, int EPI, int ABL = 0>
-bool launch6(const CatsegGemmArgs* g, hipStream_t st) {
-  if (g->N % BN != 0 || g->K % 64 != 0) return false;
-  const bool ident = g->amap.d1 == 1 && g->amap.m1 >= g->M && g->amap.s1 == 1 && g->amap.m2 == 1 && g->amap.off == 0;
-  if (!ident) return false;
-  const EpiArgs e = make_epi(g, sizeof(TO));
-  const int tm = (int)((g->M + BM - 1) / BM), tn = (int)(g->N / BN);
-  auto kern = gemm6_kernel<TO, BM, BN, EPI, ABL>;
-  g_gemm_last = ABL == 0 ? (BM == 320 ? (BN == 256 ? 50 : 51) : 52) : (BM == 256 ? 55 + ABL : 57 + ABL);
-  // the kernel's choice of wide_epilogue_bf16, whose stores are the only ones with a write-through form
-  g_gemm_last_wt = sizeof(TO) == 2 && (BM / 32) % 2 == 0 && (e.pf & 2) && !(EPI == 1 && e.res) && !(e.pf & 4) && (e.pf & 8);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(tm * tn)), dim3(512), 0, st, (const bf16*)g->A, g->lda, (const bf16*)g->W,
-                     g->ldw, g->M, g->K, tn, e, std::max(1, g_gemm4_group));
+// The tiles of gemm3_kernel (bf16 and fp8 operands) and gemm6_kernel: the ONLY place that says which
+// exist.  The automatic choice, the forced variants (gemm_variant / gemm_fp8_variant = id), the scatter
+// restriction, the instantiations and gemm_last all read it.  To add a tile: add a row, with the mask of
+// the epilogues it is to be instantiated for.  Ids are test / tool vocabulary, unique per operand type.
+enum Family : int { GEMM3, GEMM3_FP8, GEMM6 };
+enum : unsigned { E0 = 1, E1 = 2, E2 = 4 };   // EPI 0 = general, 1 = bias (+ res), 2 = bias + QuickGELU
+struct Tile {
+  int id; Family fam;
+  int bm, bn, wgm, wgn, s, bk;   // tile, waves (m x n), ring depth, K-step in 2-byte units (fp8: 2x the fp8 K depth)
+  int slots;                     // workgroups per CU
+  float w;                       // measured per-CU efficiency for the automatic score; 0 = not an automatic candidate
+  unsigned epi;                  // the EPI forms instantiated (E0 | E1 | E2)
+  bool sc;                       // also the ConvTranspose scatter form (EPI 0, SC)
+};
+// Automatic bf16 weights: tools/micro_gemm.py on one box (MG_M for other M).  M = 4616 (bs 8): QKV 224x256
+// 35.1 us (hipBLASLt 32.3), fc1 160x128 two per CU 54.2 (256x256: 71.3), out-proj / fc2 160x128 BK=128
+// 19.8 / 47.9; M = 2308 (bs 4, config 4): QKV 128x128 8-wave two per CU 22.9 vs 24.2, fc1 160x128 two per
+// CU 31.4 (256x256: 47.6), out-proj / fc2 96x128 BK=128 13.9 / 35.2 vs 18.8 / 50.9.  gemm6 (round 6): fc1
+// 41.2 us vs 47.3 for 160x128 two per CU, QKV 31.4 vs 33.3 for 224x256; weights from those ratios.
+// (Measured and dropped: bf16 160x128 with ring depth 3 / 4, slower on fc2; a one-round 320x256 gemm3 fc1
+// tile, 58.4 us vs 54.5; 288x256, 102 us.)  Equal scores keep the earlier row.
+constexpr Tile TILES[] = {
+    {20, GEMM3, 224, 256, 2, 4, 2, 64, 1, 1.0f, E0 | E1 | E2, false},
+    {1, GEMM3, 256, 256, 2, 4, 2, 64, 1, 0.95f, E0, false},
+    {15, GEMM3, 160, 128, 2, 4, 2, 128, 1, 0.95f, E0 | E1 | E2, true},
+    {17, GEMM3, 160, 128, 2, 4, 2, 64, 2, 0.9f, E0 | E1 | E2, true},
+    {19, GEMM3, 128, 128, 2, 4, 2, 64, 2, 0.85f, E0 | E1 | E2, false},
+    {24, GEMM3, 96, 128, 2, 4, 2, 128, 1, 0.85f, E0 | E1 | E2, false},
+    // the wide ping-pong tiles: lean epilogues only; gemm6_kernel is 2 x 4 waves, 2 slots of BK 64
+    {50, GEMM6, 320, 256, 2, 4, 2, 64, 1, 1.1f, E1 | E2, false},
+    {51, GEMM6, 320, 192, 2, 4, 2, 64, 1, 1.1f, E1 | E2, false},
+    {52, GEMM6, 256, 256, 2, 4, 2, 64, 1, 0.f, E1 | E2, false},
+    // fp8 (catseg_gemm_fp8): chosen by launch_f8's own rule, not by score
+    {1, GEMM3_FP8, 256, 256, 2, 4, 2, 64, 1, 0.f, E0, false},
+    {15, GEMM3_FP8, 160, 128, 2, 4, 2, 128, 1, 0.f, E0 | E1 | E2, false},
+    {17, GEMM3_FP8, 160, 128, 2, 4, 2, 64, 2, 0.f, E0 | E1 | E2, false},
+    {19, GEMM3_FP8, 128, 128, 2, 4, 2, 64, 2, 0.f, E0, false},
+    {20, GEMM3_FP8, 224, 256, 2, 4, 2, 64, 1, 0.f, E0 | E1 | E2, false},
+    {21, GEMM3_FP8, 160, 128, 2, 4, 3, 64, 1, 0.f, E0, false},
+    {23, GEMM3_FP8, 160, 256, 2, 4, 3, 64, 1, 0.f, E0, false},
+    {24, GEMM3_FP8, 160, 256, 2, 4, 2, 64, 1, 0.f, E0, false},
+};
+constexpr int NTILES = sizeof(TILES) / sizeof(TILES[0]);
+
+// row of the bf16 (gemm3 / gemm6) or fp8 tile `id`, -1 = none
+constexpr int find_tile(bool fp8, int id) {
+  for (int i = 0; i < NTILES; ++i)
+    if ((TILES[i].fam == GEMM3_FP8) == fp8 && TILES[i].id == id) return i;
+  return -1;
+}
+
+struct Call { const CatsegGemmArgs* g; const float* sa; const float* sw; hipStream_t st; };   // sa / sw: fp8 scales
+
+// gemm3 tile TILES[I].  fp8: g's K / lda / ldw are in fp8 elements (bytes), the kernel sees 2-byte units;
+// gemm_last / gemm_last_wt report the bf16 launches only
+template <typename TO, int I, int EPI, bool SC>
+bool launch3(const Call& c) {
+  constexpr Tile T = TILES[I];
+  constexpr bool F8 = T.fam == GEMM3_FP8;
+  constexpr int U = F8 ? 2 : 1;
+  const CatsegGemmArgs* g = c.g;
+  if (g->N % T.bn != 0 || (g->K / U) % T.bk != 0) return false;
+  EpiArgs e = make_epi(g, epi_forms(g, sizeof(TO)));
+  e.sa = c.sa; e.sw = c.sw;
+  const int tm = (int)((g->M + T.bm - 1) / T.bm), tn = (int)(g->N / T.bn);
+  if constexpr (!F8) {
+    g_gemm_last = T.id;
+    g_gemm_last_wt = Gemm3Lean<T.bm, T.bn, T.wgm, T.wgn, EPI, SC>::ONE && (e.pf & EF_PREFETCH) && sizeof(TO) == 4 &&
+                     !(e.pf & EF_G3_NT) && (e.pf & EF_G3_WT);
+  }
+  hipLaunchKernelGGL((gemm3_kernel<TO, T.bm, T.bn, T.wgm, T.wgn, T.s, T.bk, F8, SC, EPI>), dim3((unsigned)(tm * tn)),
+                     dim3(64 * T.wgm * T.wgn), 0, c.st, (const bf16*)g->A, g->lda / U, to_rowmap(g->amap), (const bf16*)g->W,
+                     g->ldw / U, g->M, g->K / U, tn, e, g_gemm_group);
   return true;
 }
 
-// the gemm_variant number of a gemm3 tile (try_gemm3's table)
-constexpr int gemm3_variant(int bm, int bn, int s, int bk) {
-  return bm == 256 ? 1 : bm == 224 ? 20 : bm == 128 ? 19 : bm == 96 ? 24 : s == 3 ? 21 : s == 4 ? 22 : bk == 128 ? 15 : 17;
-}
-
-template <typename TO, int BM, int BN, int WGM, int WGN, int S, int BK, bool SC = false, int EPI = 0>
-bool launch3(const CatsegGemmArgs* g, hipStream_t st) {
-  if (g->N % BN != 0 || g->K % BK != 0) return false;
-  const EpiArgs e = make_epi(g, sizeof(TO));
-  RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
-  const int tm = (int)((g->M + BM - 1) / BM), tn = (int)(g->N / BN);
-  g_gemm_last = gemm3_variant(BM, BN, S, BK);
-  g_gemm_last_wt = Gemm3Lean<BM, BN, WGM, WGN, EPI, SC>::ONE && (e.pf & 1) && sizeof(TO) == 4 && !(e.pf & 16) && (e.pf & 32);
-  hipLaunchKernelGGL((gemm3_kernel<TO, BM, BN, WGM, WGN, S, BK, false, SC, EPI>), dim3((unsigned)(tm * tn)), dim3(64 * WGM * WGN), 0,
-                     st, (const bf16*)g->A, g->lda, am, (const bf16*)g->W, g->ldw, g->M, g->K, tn, e, g_gemm_group);
+// the wide ping-pong tile TILES[I] (gemm6): needs an identity A map (32-bit buffer offsets: try_gemm3's wide_ok)
+template <typename TO, int I, int EPI>
+bool launch6(const Call& c) {
+  constexpr Tile T = TILES[I];
+  static_assert(T.wgm == 2 && T.wgn == 4 && T.s == 2 && T.bk == 64, "gemm6_kernel's fixed geometry");
+  const CatsegGemmArgs* g = c.g;
+  if (g->N % T.bn != 0 || g->K % T.bk != 0) return false;
+  if (!is_identity(g->amap, g->M)) return false;
+  const EpiArgs e = make_epi(g, epi_forms(g, sizeof(TO)));
+  const int tm = (int)((g->M + T.bm - 1) / T.bm), tn = (int)(g->N / T.bn);
+  g_gemm_last = T.id;
+  g_gemm_last_wt = Gemm6Reg<TO, T.bm>::CAN && GEMM6_REG_USE(EPI, e) && !(e.pf & EF_WIDE_NT) && (e.pf & EF_WIDE_WT);
+  hipLaunchKernelGGL((gemm6_kernel<TO, T.bm, T.bn, EPI>), dim3((unsigned)(tm * tn)), dim3(512), 0, c.st, (const bf16*)g->A,
+                     g->lda, (const bf16*)g->W, g->ldw, g->M, g->K, tn, e, std::max(1, g_gemm4_group));
   return true;
 }
 
-// fp8: g's K / lda / ldw are in fp8 elements (bytes); the kernel sees 2-byte units
-template <typename TO, int BM, int BN, int WGM, int WGN, int S, int BK, int EPI = 0>
-bool launch3f8(const CatsegGemmArgs* g, const float* sa, const float* sw, hipStream_t st) {
-  if (g->N % BN != 0 || (g->K / 2) % BK != 0) return false;
-  EpiArgs e = make_epi(g, sizeof(TO));
-  e.sa = sa; e.sw = sw;
-  RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
-  const int tm = (int)((g->M + BM - 1) / BM), tn = (int)(g->N / BN);
-  hipLaunchKernelGGL((gemm3_kernel<TO, BM, BN, WGM, WGN, S, BK, true, false, EPI>), dim3((unsigned)(tm * tn)), dim3(64 * WGM * WGN),
-                     0, st, (const bf16*)g->A, g->lda / 2, am, (const bf16*)g->W, g->ldw / 2, g->M, g->K / 2, tn, e,
-                     g_gemm_group);
-  return true;
+// TILES[I] with epilogue EPI (SC: the scatter form); false where the table has no such instantiation
+template <typename TO, int I, int EPI, bool SC = false>
+bool launch_form(const Call& c) {
+  constexpr Tile T = TILES[I];
+  if constexpr (SC ? !T.sc : !(T.epi >> EPI & 1)) return false;
+  else if constexpr (T.fam == GEMM6) return launch6<TO, I, EPI>(c);
+  else return launch3<TO, I, EPI, SC>(c);
+}
+// a lean epilogue the tile is not instantiated for runs as the general one
+template <typename TO, int I>
+bool launch_row(const Call& c, int epi, bool scatter) {
+  if (scatter) return launch_form<TO, I, 0, true>(c);
+  if (!(TILES[I].epi >> epi & 1)) epi = 0;
+  return epi == 1 ? launch_form<TO, I, 1>(c) : epi == 2 ? launch_form<TO, I, 2>(c) : launch_form<TO, I, 0>(c);
+}
+using Rows = std::make_integer_sequence<int, NTILES>;
+template <typename TO, int... I>
+bool launch_tile(int row, const Call& c, int epi, bool scatter, std::integer_sequence<int, I...>) {
+  bool ok = false;
+  (void)((row == I && ((ok = launch_row<TO, I>(c, epi, scatter)), true)) || ...);
+  return ok;   // row -1 (no such tile): nothing launched
 }
 
-int g_gemm_wide = 1;      // 1 = the automatic choice includes the wide ping-pong tiles (gemm6); 0 = round-5 candidates
-int g_gemm_variant = 0;   // 0 = automatic; >0 forces one of the automatic gemm3 tiles (tests / tuning)
+// the lean epilogues: 1 = bias (+ res), 2 = bias + QuickGELU, 0 = everything else
+int lean_epi(const CatsegGemmArgs* g) {
+  const bool plain = !g->add && !g->res2 && g->alpha == 1.f;
+  return plain && g->act == ACT_NONE ? 1 : plain && g->act == ACT_QUICKGELU && !g->res ? 2 : 0;
+}
 
-// returns true when a gemm3 variant was launched
+// returns true when a gemm3 / gemm6 tile was launched
 template <typename TO>
 bool try_gemm3(const CatsegGemmArgs* g, hipStream_t st) {
   if (g->K % 32 != 0 || g->lda % 8 != 0 || g->ldw % 8 != 0) return false;
@@ -1126,130 +1219,55 @@ bool try_gemm3(const CatsegGemmArgs* g, hipStream_t st) {
   if (g->res && (g->ld_res % 8 != 0 || ((uintptr_t)g->res % 16) != 0)) return false;
   if (g->res2 && (g->ld_res2 % 8 != 0 || ((uintptr_t)g->res2 % 16) != 0)) return false;
   if (g->add && (g->add_ncols % 8 != 0 || g->ld_add % vo != 0 || ((uintptr_t)g->add % 16) != 0)) return false;
-  int v = g_gemm_variant;
-  if (v < 0) return false;
-  if (v == 0) {
+  if (g_gemm_variant < 0) return false;
+  const bool scatter = g->store_mode != 0;
+  int row = find_tile(false, g_gemm_variant);   // a number that names no tile: gemm2_kernel
+  if (g_gemm_variant == 0) {
     if (g->M < 1024 || g->K < 256) return false;
-    // Tile choice by wave quantization over the 256 CUs (tools/micro_gemm.py, MG_M for other M):
-    // score = fill x w / (1 + 0.15 (rounds - 1)), fill = tiles / (rounds x slots), slots = 256
-    // or 512 (two workgroups per CU), w = the tile's measured per-CU efficiency.  Picks, e.g.:
-    //  M = 4616 (bs 8): QKV 224x256 (35.1 us; hipBLASLt 32.3), fc1 160x128 two per CU (54.2 vs
-    //    71.3 for 256x256), out-proj / fc2 160x128 BK=128 (19.8 / 47.9 us);
-    //  M = 2308 (bs 4, config 4): QKV 128x128 8-wave two per CU (22.9 vs 24.2 us), fc1 160x128
-    //    two per CU (31.4 vs 47.6 for 256x256), out-proj / fc2 96x128 BK=128 (13.9 / 35.2 vs
-    //    18.8 / 50.9 us).
-    // (Earlier measurements: deeper rings S = 3 / 4 slower on fc2; a one-round 320x256 fc1 tile
-    // 58.4 us vs 54.5; 288x256 102 us.)  The tile never changes the arithmetic: every variant
-    // accumulates the full K of an output in the same k order.
-    // The ping-pong wide tiles (gemm6, v 50 / 51) need an identity A map and 32-bit buffer offsets.
-    // (round 6, tools/micro_gemm.py, one box: fc1 41.2 us vs 47.3 for 160x128 two per CU, QKV 31.4
-    // vs 33.3 for 224x256; weights from those ratios)
-    struct Cand { int v, bm, bn, slots, bk; float w; };
-    static const Cand cands[] = {{20, 224, 256, 1, 64, 1.0f}, {1, 256, 256, 1, 64, 0.95f}, {15, 160, 128, 1, 128, 0.95f},
-                                 {17, 160, 128, 2, 64, 0.9f}, {19, 128, 128, 2, 64, 0.85f}, {24, 96, 128, 1, 128, 0.85f},
-                                 {50, 320, 256, 1, 64, 1.1f}, {51, 320, 192, 1, 64, 1.1f}};
-    const bool ident = g->amap.d1 == 1 && g->amap.m1 >= g->M && g->amap.s1 == 1 && g->amap.m2 == 1 && g->amap.off == 0;
-    const bool lean = !g->add && !g->res2 && g->alpha == 1.f &&
-                      (g->act == ACT_NONE || (g->act == ACT_QUICKGELU && !g->res)) && g->store_mode == 0;
-    const bool wide_ok = g_gemm_wide && ident && lean && g->M * g->lda * 2 < 0x7fffffffLL && g->N * g->ldw * 2 < 0x7fffffffLL;
+    // Tile choice by wave quantization over the 256 CUs: score = fill x w / (1 + 0.15 (rounds - 1)),
+    // fill = tiles / (rounds x slots), slots = 256 x workgroups per CU.  The tile never changes the
+    // arithmetic: every variant accumulates the full K of an output in the same k order.
+    // The ping-pong wide tiles (gemm6) need an identity A map, a lean epilogue and 32-bit buffer offsets.
+    const bool wide_ok = g_gemm_wide && is_identity(g->amap, g->M) && lean_epi(g) != 0 && !scatter &&
+                         fits_31bit(g->M * g->lda, 2) && fits_31bit(g->N * g->ldw, 2);
     float best = 0.f;
-    for (const Cand& c : cands) {
-      if (g->N % c.bn != 0 || g->K % c.bk != 0) continue;
-      if (c.v >= 50 && !wide_ok) continue;
-      const int64_t tiles = ((g->M + c.bm - 1) / c.bm) * (g->N / c.bn), slots = 256LL * c.slots;
+    for (int i = 0; i < NTILES; ++i) {
+      const Tile& t = TILES[i];
+      if (t.fam == GEMM3_FP8 || t.w == 0.f) continue;
+      if (g->N % t.bn != 0 || g->K % t.bk != 0) continue;
+      if (t.fam == GEMM6 && !wide_ok) continue;
+      const int64_t tiles = ((g->M + t.bm - 1) / t.bm) * (g->N / t.bn), slots = 256LL * t.slots;
       const int64_t rounds = (tiles + slots - 1) / slots;
-      const float score = (float)tiles / (float)(rounds * slots) * c.w / (1.f + 0.15f * (float)(rounds - 1));
-      if (score > best) { best = score; v = c.v; }
+      const float score = (float)tiles / (float)(rounds * slots) * t.w / (1.f + 0.15f * (float)(rounds - 1));
+      if (score > best) { best = score; row = i; }
     }
-    if (v == 0) return false;
-  }
-  if (g->store_mode != 0) {   // ConvTranspose scatter epilogue: instantiated for the 160x128 tiles only
-    int sv = v;
-    if (g_gemm_variant == 0 && sv != 15 && sv != 17) sv = g->K % 128 == 0 ? 15 : 17;
-    if (sv == 15) return launch3<TO, 160, 128, 2, 4, 2, 128, true>(g, st);
-    if (sv == 17) return launch3<TO, 160, 128, 2, 4, 2, 64, true>(g, st);
-    return false;
-  }
-  // lean epilogues for the automatic ViT tiles
-  const bool plain = !g->add && !g->res2 && g->alpha == 1.f;
-  const int epi = plain && g->act == ACT_NONE ? 1 : plain && g->act == ACT_QUICKGELU && !g->res ? 2 : 0;
-  if (epi == 1 && v == 15) return launch3<TO, 160, 128, 2, 4, 2, 128, false, 1>(g, st);
-  if (epi == 1 && v == 17) return launch3<TO, 160, 128, 2, 4, 2, 64, false, 1>(g, st);
-  if (epi == 1 && v == 20) return launch3<TO, 224, 256, 2, 4, 2, 64, false, 1>(g, st);
-  if (epi == 2 && v == 15) return launch3<TO, 160, 128, 2, 4, 2, 128, false, 2>(g, st);
-  if (epi == 2 && v == 17) return launch3<TO, 160, 128, 2, 4, 2, 64, false, 2>(g, st);
-  if (epi == 2 && v == 20) return launch3<TO, 224, 256, 2, 4, 2, 64, false, 2>(g, st);
-  if (epi == 1 && v == 19) return launch3<TO, 128, 128, 2, 4, 2, 64, false, 1>(g, st);
-  if (epi == 2 && v == 19) return launch3<TO, 128, 128, 2, 4, 2, 64, false, 2>(g, st);
-  if (epi == 1 && v == 24) return launch3<TO, 96, 128, 2, 4, 2, 128, false, 1>(g, st);
-  if (epi == 1 && v == 21) return launch3<TO, 160, 128, 2, 4, 3, 64, false, 1>(g, st);
-  if (epi == 2 && v == 21) return launch3<TO, 160, 128, 2, 4, 3, 64, false, 2>(g, st);
-  if (epi == 1 && v == 22) return launch3<TO, 160, 128, 2, 4, 4, 64, false, 1>(g, st);
-  if (epi == 2 && v == 22) return launch3<TO, 160, 128, 2, 4, 4, 64, false, 2>(g, st);
-  if (epi == 2 && v == 24) return launch3<TO, 96, 128, 2, 4, 2, 128, false, 2>(g, st);
-  // wide ping-pong tiles (gemm6, lean epilogues only); 56-60: timing ablations (wrong outputs)
-  if (v >= 50 && v < 70 && (epi == 1 || epi == 2)) {
-    const bool e1 = epi == 1;
-    switch (v) {
-      case 50: return e1 ? launch6<TO, 320, 256, 1>(g, st) : launch6<TO, 320, 256, 2>(g, st);
-      case 51: return e1 ? launch6<TO, 320, 192, 1>(g, st) : launch6<TO, 320, 192, 2>(g, st);
-      case 52: return e1 ? launch6<TO, 256, 256, 1>(g, st) : launch6<TO, 256, 256, 2>(g, st);
-      case 56: return launch6<TO, 256, 256, 1, 1>(g, st);   // no LDS-DMA
-      case 57: return launch6<TO, 256, 256, 1, 2>(g, st);   // no MFMA
-      case 58: return launch6<TO, 320, 256, 2, 1>(g, st);   // the fc1 tile: no LDS-DMA
-      case 59: return launch6<TO, 320, 256, 2, 2>(g, st);   //                no MFMA
-      case 60: return launch6<TO, 320, 256, 2, 3>(g, st);   //                no epilogue
-      default: return false;
+    if (row < 0) return false;
+    if (scatter && !TILES[row].sc) {   // the first tile with the scatter form whose K-step divides K
+      row = -1;
+      for (int i = 0; i < NTILES && row < 0; ++i)
+        if (TILES[i].sc && g->K % TILES[i].bk == 0) row = i;
     }
   }
-  // forced tiles (gemm_variant, tests / tools/micro_gemm.py): the automatic candidates only
-  switch (v) {
-    case 1: return launch3<TO, 256, 256, 2, 4, 2, 64>(g, st);
-    case 15: return launch3<TO, 160, 128, 2, 4, 2, 128>(g, st);
-    case 17: return launch3<TO, 160, 128, 2, 4, 2, 64>(g, st);
-    case 19: return launch3<TO, 128, 128, 2, 4, 2, 64>(g, st);
-    case 20: return launch3<TO, 224, 256, 2, 4, 2, 64>(g, st);
-    case 24: return launch3<TO, 96, 128, 2, 4, 2, 128>(g, st);
-    default: return false;
-  }
+  return launch_tile<TO>(row, Call{g, nullptr, nullptr, st}, lean_epi(g), scatter, Rows{});
 }
 
+// the generic kernels: no tile table, no epilogue forms
 template <typename TA, typename TO, int BM, int BN>
 void launch(const CatsegGemmArgs* g, hipStream_t st) {
-  EpiArgs e;
-  e.bias = g->bias;
-  e.add = g->add; e.ld_add = g->ld_add; e.add_ncols = g->add_ncols;
-  e.addmap = RowMap{g->addmap.d1, g->addmap.m1, g->addmap.s1, g->addmap.d2, g->addmap.m2, g->addmap.s2, g->addmap.off};
-  e.act = g->act; e.alpha = g->alpha;
-  e.res = g->res; e.ld_res = g->ld_res; e.res2 = g->res2; e.ld_res2 = g->ld_res2;
-  e.out = g->out; e.ldo = g->ldo;
-  e.store_mode = g->store_mode; e.cvt_k = g->cvt_k; e.cvt_hin = g->cvt_hin; e.cvt_win = g->cvt_win;
-  e.cvt_cout = g->cvt_cout;
-  RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
   dim3 grid((unsigned)((g->M + BM - 1) / BM), (unsigned)((g->N + BN - 1) / BN));
   g_gemm_last = 3;
   g_gemm_last_wt = 0;
-  hipLaunchKernelGGL((gemm_kernel<TA, TO, BM, BN>), grid, dim3(NT), 0, st,
-                     (const TA*)g->A, g->lda, am, (const TA*)g->W, g->ldw, g->M, g->N, g->K, e);
+  hipLaunchKernelGGL((gemm_kernel<TA, TO, BM, BN>), grid, dim3(NT), 0, st, (const TA*)g->A, g->lda, to_rowmap(g->amap),
+                     (const TA*)g->W, g->ldw, g->M, g->N, g->K, make_epi(g));
 }
 
 template <typename TO, int BM, int BN>
 void launch2(const CatsegGemmArgs* g, hipStream_t st) {
-  EpiArgs e;
-  e.bias = g->bias;
-  e.add = g->add; e.ld_add = g->ld_add; e.add_ncols = g->add_ncols;
-  e.addmap = RowMap{g->addmap.d1, g->addmap.m1, g->addmap.s1, g->addmap.d2, g->addmap.m2, g->addmap.s2, g->addmap.off};
-  e.act = g->act; e.alpha = g->alpha;
-  e.res = g->res; e.ld_res = g->ld_res; e.res2 = g->res2; e.ld_res2 = g->ld_res2;
-  e.out = g->out; e.ldo = g->ldo;
-  e.store_mode = g->store_mode; e.cvt_k = g->cvt_k; e.cvt_hin = g->cvt_hin; e.cvt_win = g->cvt_win;
-  e.cvt_cout = g->cvt_cout;
-  RowMap am{g->amap.d1, g->amap.m1, g->amap.s1, g->amap.d2, g->amap.m2, g->amap.s2, g->amap.off};
   const int tm = (int)((g->M + BM - 1) / BM), tn = (int)((g->N + BN - 1) / BN);
   g_gemm_last = 2;
   g_gemm_last_wt = 0;
   hipLaunchKernelGGL((gemm2_kernel<TO, BM, BN>), dim3((unsigned)(tm * tn)), dim3(NT), 0, st, (const bf16*)g->A,
-                     g->lda, am, (const bf16*)g->W, g->ldw, g->M, g->N, g->K, tn, e);
+                     g->lda, to_rowmap(g->amap), (const bf16*)g->W, g->ldw, g->M, g->N, g->K, tn, make_epi(g));
 }
 
 template <typename TA, typename TO>
@@ -1270,42 +1288,29 @@ void launch_tiles(const CatsegGemmArgs* g, hipStream_t st) {
   }
 }
 
-int g_gemm_f8_variant = 0;   // 0 = automatic
-
-// fp8 tiles (sizes in output rows x cols; BK in 2-byte units, i.e. 2x the fp8 K depth)
+// fp8: the automatic rule is its own (not the bf16 score): one round of <= 256 tiles of the 224x256 or
+// the 160x128 BK-128 tile where that fills most CUs, else 160x128 two per CU, else 128x128
 template <typename TO>
 bool launch_f8(const CatsegGemmArgs* g, const float* sa, const float* sw, hipStream_t st) {
-  int v = g_gemm_f8_variant;
-  if (v == 0) {
-    // same wave-quantization rule as the bf16 tiles (one round of <= 256 tiles)
-    const int64_t t224 = ((g->M + 223) / 224) * (g->N / 256);
-    const int64_t t160 = ((g->M + 159) / 160) * (g->N / 128);
-    if (g->N % 256 == 0 && g->K % 128 == 0 && t224 >= 200 && t224 <= 256) v = 20;
-    else if (g->N % 128 == 0 && g->K % 256 == 0 && t160 >= 160 && t160 <= 256) v = 15;
-    else if (g->N % 128 == 0 && g->K % 128 == 0 && t160 > 256) v = 17;
-    else if (g->N % 128 == 0 && g->K % 128 == 0) v = 19;
+  int id = g_gemm_f8_variant;
+  if (id == 0) {
+    auto tile = [](int v) -> const Tile& { return TILES[find_tile(true, v)]; };
+    auto fits = [&](int v) { return g->N % tile(v).bn == 0 && g->K % (2 * tile(v).bk) == 0; };   // K in fp8 elements
+    auto tiles = [&](int v) { return ((g->M + tile(v).bm - 1) / tile(v).bm) * (g->N / tile(v).bn); };
+    if (fits(20) && tiles(20) >= 200 && tiles(20) <= 256) id = 20;
+    else if (fits(15) && tiles(15) >= 160 && tiles(15) <= 256) id = 15;
+    else if (fits(17) && tiles(17) > 256) id = 17;
+    else if (fits(19)) id = 19;
     else return false;
   }
-  // lean epilogues (bias / bias + residual, bias + QuickGELU) for the automatic tiles, as in try_gemm3
-  const bool plain = !g->add && !g->res2 && g->alpha == 1.f;
-  const int epi = plain && g->act == ACT_NONE ? 1 : plain && g->act == ACT_QUICKGELU && !g->res ? 2 : 0;
-  if (epi == 1 && v == 15) return launch3f8<TO, 160, 128, 2, 4, 2, 128, 1>(g, sa, sw, st);
-  if (epi == 1 && v == 17) return launch3f8<TO, 160, 128, 2, 4, 2, 64, 1>(g, sa, sw, st);
-  if (epi == 1 && v == 20) return launch3f8<TO, 224, 256, 2, 4, 2, 64, 1>(g, sa, sw, st);
-  if (epi == 2 && v == 15) return launch3f8<TO, 160, 128, 2, 4, 2, 128, 2>(g, sa, sw, st);
-  if (epi == 2 && v == 17) return launch3f8<TO, 160, 128, 2, 4, 2, 64, 2>(g, sa, sw, st);
-  if (epi == 2 && v == 20) return launch3f8<TO, 224, 256, 2, 4, 2, 64, 2>(g, sa, sw, st);
-  switch (v) {
-    case 1: return launch3f8<TO, 256, 256, 2, 4, 2, 64>(g, sa, sw, st);
-    case 15: return launch3f8<TO, 160, 128, 2, 4, 2, 128>(g, sa, sw, st);
-    case 17: return launch3f8<TO, 160, 128, 2, 4, 2, 64>(g, sa, sw, st);
-    case 19: return launch3f8<TO, 128, 128, 2, 4, 2, 64>(g, sa, sw, st);
-    case 20: return launch3f8<TO, 224, 256, 2, 4, 2, 64>(g, sa, sw, st);
-    case 21: return launch3f8<TO, 160, 128, 2, 4, 3, 64>(g, sa, sw, st);
-    case 23: return launch3f8<TO, 160, 256, 2, 4, 3, 64>(g, sa, sw, st);
-    case 24: return launch3f8<TO, 160, 256, 2, 4, 2, 64>(g, sa, sw, st);
-    default: return false;
-  }
+  return launch_tile<TO>(find_tile(true, id), Call{g, sa, sw, st}, lean_epi(g), false, Rows{});
+}
+
+// the checks catseg_gemm and catseg_gemm_fp8 share (row-map sanity; their alignment rules differ): the
+// message to put after the entry point's prefix, nullptr = fine
+const char* shared_arg_error(const CatsegGemmArgs* g) {
+  auto ok = [](const CatsegRowMap& m) { return m.d1 > 0 && m.m1 > 0 && m.d2 > 0 && m.m2 > 0; };
+  return !ok(g->amap) ? "bad amap" : g->add && !ok(g->addmap) ? "bad addmap" : nullptr;
 }
 
 }  // namespace
@@ -1336,9 +1341,7 @@ extern "C" int catseg_gemm_fp8(const CatsegGemmArgs* g, const float* scale_a, co
   CATSEG_CHECK(!g->res2 || (g->ld_res2 % 8 == 0 && ((uintptr_t)g->res2 % 16) == 0), "gemm_fp8: res2 rows must be 16B aligned");
   CATSEG_CHECK(!g->add || (g->add_ncols % 8 == 0 && g->ld_add % 8 == 0 && ((uintptr_t)g->add % 16) == 0),
                "gemm_fp8: add rows must be 16B aligned");
-  CATSEG_CHECK(g->amap.d1 > 0 && g->amap.m1 > 0 && g->amap.d2 > 0 && g->amap.m2 > 0, "gemm_fp8: bad amap");
-  CATSEG_CHECK(!g->add || (g->addmap.d1 > 0 && g->addmap.m1 > 0 && g->addmap.d2 > 0 && g->addmap.m2 > 0),
-               "gemm_fp8: bad addmap");
+  if (const char* m = shared_arg_error(g)) { catseg_set_error("gemm_fp8: %s", m); return CATSEG_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   bool ok;
   if (g->dtype_out == CATSEG_BF16) ok = launch_f8<bf16>(g, scale_a, scale_w, st);
@@ -1363,9 +1366,7 @@ extern "C" int catseg_gemm(const CatsegGemmArgs* g, void* stream) {
   CATSEG_CHECK(g->store_mode == 0 || g->N == (int64_t)g->cvt_k * g->cvt_k * g->cvt_cout,
                "gemm: ConvTranspose N must be k*k*cout");
   CATSEG_CHECK(g->store_mode == 0 || g->M < (1LL << 31), "gemm: ConvTranspose row count must fit 31 bits");
-  CATSEG_CHECK(g->amap.d1 > 0 && g->amap.m1 > 0 && g->amap.d2 > 0 && g->amap.m2 > 0, "gemm: bad amap");
-  CATSEG_CHECK(!g->add || (g->addmap.d1 > 0 && g->addmap.m1 > 0 && g->addmap.d2 > 0 && g->addmap.m2 > 0),
-               "gemm: bad addmap");
+  if (const char* m = shared_arg_error(g)) { catseg_set_error("gemm: %s", m); return CATSEG_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   if (g->dtype_a == CATSEG_BF16 && g->dtype_out == CATSEG_BF16) launch_tiles<bf16, bf16>(g, st);
   else if (g->dtype_a == CATSEG_BF16 && g->dtype_out == CATSEG_F32) launch_tiles<bf16, float>(g, st);

@@ -194,7 +194,7 @@ int rownorm(const void* in, int64_t ld_in, CatsegRowMap m, int dti, void* out, i
     const int64_t cap = g_ln_variant == 2 ? 256 : g_ln_variant == 3 ? 1024 : 512;
     const unsigned pg = (unsigned)std::min<int64_t>((rows + 3) / 4, cap);
     // write-through only when every byte offset of the output fits its 31-bit offset
-    const bool wt = g_ln_store && wt_fits(rows * ld_out, 2);
+    const bool wt = g_ln_store && fits_31bit(rows * ld_out, 2);
     g_ln_last = wt ? 2 : 1;
     if (wt) hipLaunchKernelGGL((ln_pipe_kernel<4, true>), dim3(pg), block, 0, st, (const float*)in, ld_in, rm, (bf16*)out, ld_out,
                                gamma, beta, rows, eps);

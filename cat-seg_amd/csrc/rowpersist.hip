@@ -870,7 +870,7 @@ int g_rows_store = 0;   // output stores of the persistent row kernels: 0 = plai
 CATSEG_KNOB(g_rows_store, "rows_store");
 // e with the write-through flag of the rows_store knob, for an output spanning `out_elems` bf16
 PEpi with_wt(PEpi e, int64_t out_elems) {
-  e.wt = g_rows_store && out_elems * 2 < 0x7fffffffLL;
+  e.wt = g_rows_store && fits_31bit(out_elems, 2);
   return e;
 }
 

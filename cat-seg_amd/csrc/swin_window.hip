@@ -623,7 +623,7 @@ int swin_win5_launch(const CatsegSwinAttnArgs* a, int n_cu, hipStream_t st, bool
   p.gmap = RowMap{a->gmap.d1, a->gmap.m1, a->gmap.s1, a->gmap.d2, a->gmap.m2, a->gmap.s2, a->gmap.off};
   p.out = (bf16*)a->out; p.ld_out = a->ld_out;
   p.shift = a->shift; p.scale = a->scale;
-  p.wt = g_swin_store && a->S * 576 * a->ld_out * 2 < 0x7fffffffLL;
+  p.wt = g_swin_store && fits_31bit(a->S * 576 * a->ld_out, 2);
   const int nwin_total = (int)(a->S * NWIN);
   const dim3 grid((unsigned)std::min(nwin_total, (2 * n_cu) / NWIN * NWIN));
   // only for guidance rows that are one base + the pixel per slice (every engine call; the caller

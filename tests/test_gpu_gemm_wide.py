@@ -1,7 +1,7 @@
 """The wide ping-pong GEMM (gemm.hip gemm6_kernel, variants 50 / 51 / 52) tested directly: every
 epilogue launch6 instantiates against fp64, strided and poisoned operands, bit identity across its
 store / epilogue / tile-order forms and against the gemm3 tiles, the automatic tile choice at the
-headline shapes, and the write-through store forms (gemm, LayerNorm, ViT attention) on outputs whose
+headline shapes and pinned over a grid of shapes, and the write-through store forms (gemm, LayerNorm, ViT attention) on outputs whose
 byte offsets pass 2 GiB.  Which kernel ran is read back from the diagnostic knobs gemm_last /
 gemm_last_wt / ln_last / attn_last_wt.  Marked gpu: runs on the MI355X box only."""
 import contextlib
@@ -264,6 +264,206 @@ def test_gemm_auto_dispatch():
         with knobs(gemm_wide=0):
             last, wt = call(4096, BF16, "auto fc1 gemm_wide 0", fc1, act=L.ACT_QUICKGELU)
         assert 0 < last < 50 and wt == 0
+
+
+GRID_M = (1024, 1200, 2308, 4616, 9232, 18464)
+GRID_N = (128, 256, 384, 768, 1024, 3072, 4096)
+GRID_K = (256, 320)                      # 320: a multiple of 64, not of 128 (the BK filter)
+GRID_EPIS = ("bias_bf16", "gelu_bf16", "res_f32")
+GRID_EXTRA = (4616, 1024, 256)           # M, N, K of the add / row-map / ConvTranspose cases
+
+
+def auto_grid_observed():
+    """{key: (gemm_last, gemm_last_wt)} of the automatic choice over the grid of test_gemm_auto_grid; keys
+    are (gemm_wide, K, epilogue, M, N) and (gemm_wide, "add" | "cls_drop" | "convt", epilogue).  Operands are
+    zero-filled, allocated once at the largest size; every call takes dense views of them."""
+    Mx, Nx, Kx = max(GRID_M), max(GRID_N), max(GRID_K)
+    Abuf = torch.zeros(Mx * Kx, device=dev, dtype=BF16)
+    Wbuf = torch.zeros(Nx * Kx, device=dev, dtype=BF16)
+    bias = torch.zeros(Nx, device=dev)
+    obuf = {BF16: torch.zeros(Mx * Nx, device=dev, dtype=BF16), F32: torch.zeros(Mx * Nx, device=dev)}
+    rbuf = torch.zeros(Mx * Nx, device=dev)
+    Me, Ne, Ke = GRID_EXTRA
+    abuf = {dt: torch.zeros(Me, Ne, device=dev, dtype=dt) for dt in (BF16, F32)}
+    B, L_ = 8, 577
+    assert B * L_ == Me
+    cls_drop = rowmap(d1=L_, s1=L_ + 1, d2=1, m2=L_, s2=1, off=1)
+    k, cout = 2, 256                     # test_gemm_convtranspose_store_pipelined's first upsampler
+    assert k * k * cout == Ne
+
+    def run(M, N, K, epi, **kw):
+        odt, act, has_res = EPIS[epi]
+        A = kw.pop("A", None)
+        if A is None:
+            A = Abuf[:M * K].view(M, K)
+        out = kw.pop("out", None)
+        if out is None:
+            out = obuf[odt][:M * N].view(M, N)
+        ops.gemm(A, Wbuf[:N * K].view(N, K), out, M=M, bias=bias[:N], act=act,
+                 res=rbuf[:M * N].view(M, N) if has_res else None, **kw)
+        return L.tuning("gemm_last"), L.tuning("gemm_last_wt")
+
+    seen = {}
+    for wide in (1, 0):
+        with knobs(gemm_variant=0, gemm_wide=wide):
+            for K in GRID_K:
+                for epi in GRID_EPIS:
+                    for M in GRID_M:
+                        for N in GRID_N:
+                            seen[(wide, K, epi, M, N)] = run(M, N, K, epi)
+            for epi in GRID_EPIS:
+                seen[(wide, "add", epi)] = run(Me, Ne, Ke, epi, add=abuf[EPIS[epi][0]])
+                seen[(wide, "cls_drop", epi)] = run(Me, Ne, Ke, epi, A=Abuf[:B * (L_ + 1) * Ke].view(-1, Ke), amap=cls_drop)
+            seen[(wide, "convt", "bias_bf16")] = run(Me, Ne, Ke, "bias_bf16", out=obuf[BF16][:Me * Ne].view(Me * k * k, cout),
+                                                     store=(k, B, L_, cout))
+    torch.cuda.synchronize()
+    return seen
+
+
+def _grid_rows(text):
+    """One row per M, one token per N: the gemm_last number, a trailing 'w' = gemm_last_wt 1."""
+    rows = [line.split() for line in text.strip().splitlines()]
+    assert len(rows) == len(GRID_M) and all(len(r) == len(GRID_N) for r in rows)
+    return {(M, N): (int(t.rstrip("w")), int(t.endswith("w"))) for M, r in zip(GRID_M, rows) for N, t in zip(GRID_N, r)}
+
+
+# (gemm_wide, K, epilogue) -> rows M = 1024 1200 2308 4616 9232 18464, columns N = 128 256 384 768 1024 3072 4096
+AUTO_GRID = {
+    (1, 256, "bias_bf16"): """
+      24   24   24   24   24   15   15
+      24   24   24   24   24   15   15
+      24   24   24   24   24   19   17
+      24   24   24   15   15  51w  50w
+      24   24   15   19   17  51w  50w
+      24   15   19  51w  50w  50w  50w
+""",
+    (1, 256, "gelu_bf16"): """
+      24   24   24   24   24   15   15
+      24   24   24   24   24   15   15
+      24   24   24   24   24   19   17
+      24   24   24   15   15  51w  50w
+      24   24   15   19   17  51w  50w
+      24   15   19  51w  50w  50w  50w
+""",
+    (1, 256, "res_f32"): """
+      24   24   24   24   24   15   15
+      24   24   24   24   24   15   15
+      24   24   24   24   24   19   17
+      24   24   24   15   15   51   50
+      24   24   15   19   17   51   50
+      24   15   19   51   50   50   50
+""",
+    (1, 320, "bias_bf16"): """
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   17
+      19   19   19   19   19  51w  50w
+      19   19   19   19   17  51w  50w
+      19   19   19  51w  50w  50w  50w
+""",
+    (1, 320, "gelu_bf16"): """
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   17
+      19   19   19   19   19  51w  50w
+      19   19   19   19   17  51w  50w
+      19   19   19  51w  50w  50w  50w
+""",
+    (1, 320, "res_f32"): """
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   17
+      19   19   19   19   19   51   50
+      19   19   19   19   17   51   50
+      19   19   19   51   50   50   50
+""",
+    (0, 256, "bias_bf16"): """
+      24   24   24   24   24   15   15
+      24   24   24   24   24   15   15
+      24   24   24   24   24   19   17
+      24   24   24   15   15   20   17
+      24   24   15   19   17   20   20
+      24   15   19   20   17   20    1
+""",
+    (0, 256, "gelu_bf16"): """
+      24   24   24   24   24   15   15
+      24   24   24   24   24   15   15
+      24   24   24   24   24   19   17
+      24   24   24   15   15   20   17
+      24   24   15   19   17   20   20
+      24   15   19   20   17   20    1
+""",
+    (0, 256, "res_f32"): """
+      24   24   24   24   24   15   15
+      24   24   24   24   24   15   15
+      24   24   24   24   24   19   17
+      24   24   24   15   15   20   17
+      24   24   15   19   17   20   20
+      24   15   19   20   17   20    1
+""",
+    (0, 320, "bias_bf16"): """
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   17
+      19   19   19   19   19   20   17
+      19   19   19   19   17   20   20
+      19   19   19   20   17   20    1
+""",
+    (0, 320, "gelu_bf16"): """
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   17
+      19   19   19   19   19   20   17
+      19   19   19   19   17   20   20
+      19   19   19   20   17   20    1
+""",
+    (0, 320, "res_f32"): """
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   19
+      19   19   19   19   19   19   17
+      19   19   19   19   19   20   17
+      19   19   19   19   17   20   20
+      19   19   19   20   17   20    1
+""",
+}
+# (gemm_wide, case, epilogue) at M = 4616, N = 1024, K = 256
+AUTO_EXTRA = {
+    (1, "add", "bias_bf16"): (15, 0),
+    (1, "cls_drop", "bias_bf16"): (15, 0),
+    (1, "add", "gelu_bf16"): (15, 0),
+    (1, "cls_drop", "gelu_bf16"): (15, 0),
+    (1, "add", "res_f32"): (15, 0),
+    (1, "cls_drop", "res_f32"): (15, 0),
+    (1, "convt", "bias_bf16"): (15, 0),
+    (0, "add", "bias_bf16"): (15, 0),
+    (0, "cls_drop", "bias_bf16"): (15, 0),
+    (0, "add", "gelu_bf16"): (15, 0),
+    (0, "cls_drop", "gelu_bf16"): (15, 0),
+    (0, "add", "res_f32"): (15, 0),
+    (0, "cls_drop", "res_f32"): (15, 0),
+    (0, "convt", "bias_bf16"): (15, 0),
+}
+
+
+def test_gemm_auto_grid():
+    """The automatic tile choice (gemm_variant 0) pinned over a grid: M x N x K x gemm_wide x three epilogues
+    (bias -> bf16, bias + QuickGELU -> bf16, bias + fp32 residual -> fp32), plus an add operand (the general
+    epilogue), a CLS-dropping row map and a ConvTranspose store at 4616 x 1024 x 256.  Only (gemm_last,
+    gemm_last_wt) is asserted, on zero-filled operands; values are covered by the tests above.  The expected
+    tables were recorded on the MI355X from the commit BEFORE the host dispatch was rebuilt around one tile
+    table (this function with a printout in place of the assertions) and pasted in: they are never to be
+    regenerated from the code under test.  The grid reaches all eight automatic candidates."""
+    want = {}
+    for (wide, K, epi), text in AUTO_GRID.items():
+        for (M, N), v in _grid_rows(text).items():
+            want[(wide, K, epi, M, N)] = v
+    want.update(AUTO_EXTRA)
+    assert len(want) == 2 * len(GRID_K) * len(GRID_EPIS) * len(GRID_M) * len(GRID_N) + 2 * 7
+    assert {v[0] for v in want.values()} >= {1, 15, 17, 19, 20, 24, 50, 51}
+    seen = auto_grid_observed()
+    assert seen.keys() == want.keys()
+    bad = {k: (seen[k], want[k]) for k in want if seen[k] != want[k]}
+    assert not bad, f"{len(bad)} of {len(want)} choices differ, (got, want): {dict(list(bad.items())[:8])}"
 
 
 # ----------------------------------------------------------------------------- e. stores past 2 GiB
