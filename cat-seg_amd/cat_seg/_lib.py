@@ -257,6 +257,7 @@ _SIGS = {
     "catseg_class_attention": [C.POINTER(ClassAttnArgs), vp],
     "catseg_resize_bilinear": [vp, i64, i32, i32, i32, i32, i32, vp, i32, i32, vp],
     "catseg_postprocess_argmax": [vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp],
+    "catseg_postprocess_tta": [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp],
     "catseg_avgpool_rows": [vp, i64, i32, i32, i32, i32, i32, vp, i32, vp],
     "catseg_upsample_add_rows": [vp, i64, i32, i32, i32, vp, i32, i32, i32, vp],
     "catseg_sliding_crops": [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp],

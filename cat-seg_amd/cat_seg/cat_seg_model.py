@@ -316,16 +316,13 @@ class CATSeg(nn.Module):
         W = max(int(i.shape[-1]) for i in images)
         return -(-H // d) * d, -(-W // d) * d
 
-    def _forward_graph(self, eng: CatSegEngine, batched_inputs: List[dict]):
-        """The eval forward as one hipGraph replay per input geometry (what bench.py times): the
-        first call of a geometry captures engine.head_logits, every call stages its images into the
-        captured canvas, replays, and resizes the captured logits into fresh output tensors."""
+    def _graph_logits(self, eng: CatSegEngine, batched_inputs: List[dict]):
+        """One hipGraph replay per input geometry: the first call of a geometry captures
+        engine.head_logits, every call stages its images into the captured canvas and replays.
+        Returns (the captured logits buffer, valid until the next call; the image sizes)."""
         images = [x["image"] for x in batched_inputs]
         H, W = self._canvas_geometry(images)
         sizes = tuple((int(i.shape[-2]), int(i.shape[-1])) for i in images)
-        n = len(batched_inputs) if self.return_all_images else 1
-        outs = tuple((int(batched_inputs[i].get("height", sizes[i][0])), int(batched_inputs[i].get("width", sizes[i][1])))
-                     for i in range(n))
         key = (id(eng), id(eng._text), len(images), H, W, sizes)
         g = self._graphs.get(key)
         dev = eng.device
@@ -350,9 +347,18 @@ class CATSeg(nn.Module):
             self._graphs[key] = g
         self._stage_canvas(eng, images, g["raw"])
         g["graph"].replay()
+        return g["logits"], sizes
+
+    def _forward_graph(self, eng: CatSegEngine, batched_inputs: List[dict]):
+        """The eval forward as one hipGraph replay per input geometry (what bench.py times), then the
+        resize of the captured logits into fresh output tensors."""
+        logits, sizes = self._graph_logits(eng, batched_inputs)
+        dev = eng.device
+        n = len(batched_inputs) if self.return_all_images else 1
+        outs = tuple((int(batched_inputs[i].get("height", sizes[i][0])), int(batched_inputs[i].get("width", sizes[i][1])))
+                     for i in range(n))
         # the resize to each image's output size runs after the replay into FRESH tensors (the caller
         # may keep the results across calls), as the eager path does
-        logits = g["logits"]
         h_l, w_l = logits.shape[-2:]
         if n > 1 and len(set(outs)) == 1 and len(set(sizes[:n])) == 1:
             # one launch for the whole batch (the engine leg's form); each result is a view of it
@@ -370,6 +376,31 @@ class CATSeg(nn.Module):
             ops.postprocess(logits[i:i + 1], out, crop=(min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))
             results.append({"sem_seg": out[0]})
         return results
+
+    def forward_logits(self, batched_inputs: List[dict]):
+        """The eval forward without the resize: (logits, crops).  `logits` is fp32 (n, T, h, w) for ALL n
+        images of the batch, whatever RETURN_ALL_IMAGES says; `crops[i] = (min(h, image_h), min(w, image_w))`
+        is the region of image i's logits that the resize reads, as `forward` computes it.  Serves the
+        eager and the hipGraph branch; on the graph branch `logits` is the captured buffer, valid until
+        the next call of the model (copy what has to outlive it).  What the device-side merge of
+        SemanticSegmentorWithTTA consumes (catseg_postprocess_tta)."""
+        if self.training:
+            raise RuntimeError("CATSeg.forward_logits is an eval entry point: call model.eval() first")
+        if self.sliding_window:
+            raise RuntimeError("CATSeg.forward_logits does not serve TEST.SLIDING_WINDOW: the sliding branch "
+                               "merges its windows before the resize and has no single logits tensor")
+        if torch.compiler.is_compiling():
+            raise RuntimeError("CATSeg.forward_logits cannot be traced by torch.compile: call it eagerly")
+        with torch.no_grad():
+            eng = self.engine
+            self.sem_seg_head.predictor.get_text_embeds()
+            if self.use_graph:
+                logits, sizes = self._graph_logits(eng, batched_inputs)
+            else:
+                raw, sizes_dev, sizes = self._batch(eng, [x["image"] for x in batched_inputs])
+                logits = eng.head_logits(raw, sizes_dev)
+            h_l, w_l = logits.shape[-2:]
+            return logits, [(min(h_l, ih), min(w_l, iw)) for ih, iw in sizes]
 
     def forward(self, batched_inputs: List[dict]):
         if self.training:

@@ -194,4 +194,8 @@ def add_cat_seg_config(cfg):
     # eval output: "probs" {"sem_seg": (T, H, W) fp32} | "labels" {"sem_seg_labels": (H, W) int32,
     # "sem_seg_score": (H, W) fp32} (the argmax map and its probability, without the volume)
     cfg.MODEL.CATSEG_HIP.OUTPUT = "probs"
+    # SemanticSegmentorWithTTA: "host" merges the views' full-size probability volumes in torch (the
+    # reference's merge; "probs" models only) | "device" merges the views' logits in one kernel
+    # (catseg_postprocess_tta) and also serves "labels" models
+    cfg.MODEL.CATSEG_HIP.TTA_MERGE = "host"
     return cfg

@@ -14,6 +14,9 @@ need the dispatcher); these are the registered surface for code that composes th
   catseg::postprocess      sigmoid + bilinear resize (catseg_postprocess; cat_seg_model.py:222-228)
   catseg::postprocess_argmax  the same fused with the argmax over the classes -> (labels, score)
                            (catseg_postprocess_argmax; + plain_train_net.py:107-116)
+  catseg::postprocess_tta, catseg::postprocess_tta_argmax  the merge of K test-time-augmentation views of
+                           one image -> probabilities / (labels, score) (catseg_postprocess_tta;
+                           test_time_augmentation.py:81-108)
   catseg::linear           y = act(x W^T + b) with a registered backward (catseg_gemm forward,
                            catseg_gemm_ex / catseg_colsum backward): the training kernels through autograd
   catseg::head_logits      the whole eval forward of a registered CATSeg model up to the logits
@@ -24,7 +27,7 @@ from __future__ import annotations
 
 import itertools
 import weakref
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -138,6 +141,46 @@ def postprocess_argmax(logits: torch.Tensor, H: int, W: int, crop_h: int, crop_w
 def _(logits, H, W, crop_h, crop_w, sigmoid):
     return (logits.new_empty((logits.shape[0], H, W), dtype=torch.int32),
             logits.new_empty((logits.shape[0], H, W), dtype=torch.float32))
+
+
+def _tta_views(logits, crop_h, crop_w, flip):
+    if not (len(crop_h) == len(crop_w) == len(flip) == logits.shape[0]):
+        raise RuntimeError(f"catseg::postprocess_tta: {logits.shape[0]} views but {len(crop_h)} / {len(crop_w)} / "
+                           f"{len(flip)} crop_h / crop_w / flip entries")
+    return list(zip(crop_h, crop_w, flip))
+
+
+@torch.library.custom_op("catseg::postprocess_tta", mutates_args=())
+def postprocess_tta(logits: torch.Tensor, H: int, W: int, crop_h: List[int], crop_w: List[int],
+                    flip: List[int]) -> torch.Tensor:
+    """The mean over K test-time-augmentation views of one image of what catseg::postprocess computes
+    per view, mirrored views (flip 1) flipped back: (K, T, h, w) fp32 -> (T, H, W) fp32
+    (catseg_postprocess_tta; test_time_augmentation.py:81-108)."""
+    probs = torch.empty(logits.shape[1], H, W, device=logits.device, dtype=torch.float32)
+    ops.postprocess_tta(logits.contiguous(), _tta_views(logits, crop_h, crop_w, flip), probs=probs)
+    return probs
+
+
+@postprocess_tta.register_fake
+def _(logits, H, W, crop_h, crop_w, flip):
+    return logits.new_empty((logits.shape[1], H, W), dtype=torch.float32)
+
+
+@torch.library.custom_op("catseg::postprocess_tta_argmax", mutates_args=())
+def postprocess_tta_argmax(logits: torch.Tensor, H: int, W: int, crop_h: List[int], crop_w: List[int],
+                           flip: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """argmax and max over T of what catseg::postprocess_tta computes, without the (T, H, W) volume:
+    (K, T, h, w) fp32 -> labels (H, W) int32, score (H, W) fp32 (catseg_postprocess_tta;
+    + plain_train_net.py:107-116)."""
+    labels = torch.empty(H, W, device=logits.device, dtype=torch.int32)
+    score = torch.empty(H, W, device=logits.device, dtype=torch.float32)
+    ops.postprocess_tta(logits.contiguous(), _tta_views(logits, crop_h, crop_w, flip), labels=labels, score=score)
+    return labels, score
+
+
+@postprocess_tta_argmax.register_fake
+def _(logits, H, W, crop_h, crop_w, flip):
+    return (logits.new_empty((H, W), dtype=torch.int32), logits.new_empty((H, W), dtype=torch.float32))
 
 
 # ------------------------------------------------------------------------------------- linear (+ backward)

@@ -558,6 +558,34 @@ def postprocess_argmax(logits, labels, score=None, *, crop=None, sigmoid=True):
     return labels
 
 
+def postprocess_tta(logits, views, *, probs=None, labels=None, score=None):
+    """Merge of K test-time-augmentation views of one image (catseg_postprocess_tta): per view the
+    sigmoid + crop + bilinear resize of `postprocess`, mirrored views flipped back, summed in view
+    order and scaled by 1 / K.  logits (K, T, h, w) fp32; views K rows (crop_h, crop_w, flip) of host
+    ints; probs (T, H, W) fp32 and / or labels (H, W) int32 (the first maximum over T) with score (H, W)
+    fp32 (that maximum) or None.  Outputs not passed are not written.  Returns (probs, labels, score)."""
+    K, T, h, w = logits.shape
+    views = [tuple(int(e) for e in v) for v in views]
+    if len(views) != K or any(len(v) != 3 for v in views):
+        raise ValueError(f"postprocess_tta: views must be {K} rows of (crop_h, crop_w, flip), got {views!r}")
+    if probs is None and labels is None:
+        raise ValueError("postprocess_tta: pass probs and / or labels")
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    H, W = (probs if probs is not None else labels).shape[-2:]
+    assert probs is None or (probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == T * H * W)
+    assert labels is None or (labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == H * W)
+    assert score is None or (score.dtype == torch.float32 and score.is_contiguous() and score.numel() == H * W)
+    table = (C.c_int32 * (3 * K))(*[e for v in views for e in v])
+    # every view's crop read once; the merged volume and / or the label map (and score) written once
+    nbytes = 4 * (T * sum(v[0] * v[1] for v in views) + (T * H * W if probs is not None else 0)
+                  + (H * W * (1 if score is None else 2) if labels is not None else 0))
+    with _rec("postprocess_tta", 0, nbytes):
+        call("catseg_postprocess_tta", logits.data_ptr(), K, T, h, w, C.cast(table, C.c_void_p),
+             0 if probs is None else probs.data_ptr(), 0 if labels is None else labels.data_ptr(),
+             0 if score is None else score.data_ptr(), H, W, _stream())
+    return probs, labels, score
+
+
 def avgpool_rows(x, out, *, S, H, W, C, pool):
     """nn.AvgPool2d(pool) over [S][H][W][C] rows -> out [S][H/ph][W/pw][C] (catseg_avgpool_rows)."""
     ph, pw = pool

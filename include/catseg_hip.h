@@ -390,6 +390,24 @@ int catseg_resize_bilinear(const float* in, int64_t B, int T, int h, int w, int 
  * LDS stage: downsampling by more than ~3.5x per axis is rejected.  B <= 65535. */
 int catseg_postprocess_argmax(const float* logits, int64_t B, int T, int h, int w, int crop_h, int crop_w,
                               int sigmoid, int32_t* labels, float* score, int H, int W, void* stream);
+/* catseg_postprocess_tta — the merge of K test-time-augmentation views of ONE image in one kernel:
+ * replaces cat_seg/test_time_augmentation.py:81-108 (flip back, sum, divide) after
+ * cat_seg_model.py:222-227 (sigmoid + sem_seg_postprocess of every view), and for the label form
+ * also the evaluator's argmax (plain_train_net.py:107-116).  The K (T, H, W) volumes are never formed.
+ *   p_k(t,y,x) = the value catseg_postprocess computes on its banded path for (h, w, crop_h_k, crop_w_k, H, W)
+ *   v_k(t,y,x) = p_k(t, y, flip_k ? W-1-x : x)
+ *   s = v_0; s = s + v_k for k = 1 .. K-1 (fp32, view order);  m = s * (1.0f / (float)K)
+ *   probs[t][y][x] = m;  labels[y][x] = first maximum of m over t;  score[y][x] = that maximum
+ * NaN ranks above every number and the first NaN wins, as catseg_postprocess_argmax.  No atomics: the
+ * result is deterministic, and labels / score equal the argmax / max of probs bit for bit.
+ * logits fp32 [K][T][h][w] on the device.  views is a HOST table int32 [K][3] = crop_h, crop_w, flip (0/1),
+ * read at call time and passed to the kernel by value: no allocation, copy or synchronise inside, so the
+ * call can be captured in a hipGraph (the table is then frozen into the graph).  1 <= K <= 32.
+ * probs fp32 [T][H][W] or NULL; labels int32 [H][W] or NULL (at least one of them); score fp32 [H][W] or
+ * NULL, only with labels.  With both probs and labels, one launch each.  Every view's tile source patch
+ * must fit the 4096-float LDS stage, as for catseg_postprocess_argmax. */
+int catseg_postprocess_tta(const float* logits, int K, int T, int h, int w, const int32_t* views,
+                           float* probs, int32_t* labels, float* score, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------
  * catseg_swin_window_attention — fused LayerNorm(norm1) + [q|k|v] projection (+ the
