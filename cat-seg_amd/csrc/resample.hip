@@ -7,6 +7,7 @@
 #include <type_traits>
 #include "common.h"
 #include "capi.h"
+#include "resize_idx.h"
 
 namespace {
 
@@ -16,14 +17,7 @@ inline unsigned grid_of(int64_t n, int64_t cap = 65536) {
   return (unsigned)(g < cap ? g : cap);
 }
 
-// PyTorch bilinear source index, align_corners=False (area_pixel_compute_source_index)
-DEV void lin_src(int dst, int in_size, float scale, int& i0, int& i1, float& l1) {
-  float src = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  i0 = (int)src;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
-// align_corners=True: src = scale * dst, scale = (in - 1) / (out - 1)
+// align_corners=False is lin_idx (resize_idx.h); align_corners=True: src = scale * dst, scale = (in - 1) / (out - 1)
 DEV void lin_src_ac(int dst, int in_size, float scale, int& i0, int& i1, float& l1) {
   const float src = scale * (float)dst;
   i0 = (int)src;
@@ -116,8 +110,8 @@ __global__ void sliding_crops_kernel(const float* __restrict__ raw, const int32_
     }
     int y0, y1, x0, x1;
     float ly, lx;
-    lin_src(Y, h, (float)h / (float)R, y0, y1, ly);
-    lin_src(X, w, (float)w / (float)R, x0, x1, lx);
+    lin_idx(Y, h, (float)h / (float)R, y0, y1, ly);
+    lin_idx(X, w, (float)w / (float)R, x0, x1, lx);
     const float* src = raw + (n * 3 + c) * (int64_t)Hc * Wc;
     crops[i] = blend(src[(int64_t)y0 * Wc + x0], src[(int64_t)y0 * Wc + x1], src[(int64_t)y1 * Wc + x0],
                      src[(int64_t)y1 * Wc + x1], ly, lx);
@@ -130,8 +124,8 @@ DEV float sigm(float v) { return 1.f / (1.f + expf(-v)); }
 DEV float up_sig(const float* __restrict__ pl, int h, int w, int k, int y, int x) {
   int y0, y1, x0, x1;
   float ly, lx;
-  lin_src(y, h, (float)h / (float)k, y0, y1, ly);
-  lin_src(x, w, (float)w / (float)k, x0, x1, lx);
+  lin_idx(y, h, (float)h / (float)k, y0, y1, ly);
+  lin_idx(x, w, (float)w / (float)k, x0, x1, lx);
   return sigm(blend(pl[y0 * w + x0], pl[y0 * w + x1], pl[y1 * w + x0], pl[y1 * w + x1], ly, lx));
 }
 
@@ -151,8 +145,8 @@ __global__ void sliding_merge_kernel(const float* __restrict__ lg, int64_t N, in
     const float* gp = lg + ((n * L + L - 1) * T + t) * plane;
     int y0, y1, x0, x1;
     float ly, lx;
-    lin_src(Y, k, sg, y0, y1, ly);
-    lin_src(X, k, sg, x0, x1, lx);
+    lin_idx(Y, k, sg, y0, y1, ly);
+    lin_idx(X, k, sg, x0, x1, lx);
     const float glob = blend(up_sig(gp, h, w, k, y0, x0), up_sig(gp, h, w, k, y0, x1), up_sig(gp, h, w, k, y1, x0),
                              up_sig(gp, h, w, k, y1, x1), ly, lx);
     float sum = 0.f, cnt = 0.f;
@@ -183,8 +177,8 @@ DEV float sigm_fast(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
 DEV float up_sig_fast(const float* __restrict__ pl, int h, int w, int k, int y, int x) {
   int y0, y1, x0, x1;
   float ly, lx;
-  lin_src(y, h, (float)h / (float)k, y0, y1, ly);
-  lin_src(x, w, (float)w / (float)k, x0, x1, lx);
+  lin_idx(y, h, (float)h / (float)k, y0, y1, ly);
+  lin_idx(x, w, (float)w / (float)k, x0, x1, lx);
   return sigm_fast(blend(pl[y0 * w + x0], pl[y0 * w + x1], pl[y1 * w + x0], pl[y1 * w + x1], ly, lx));
 }
 
@@ -201,8 +195,8 @@ __global__ __launch_bounds__(256) void sliding_merge_band_kernel(const float* __
   const float sg = (float)k / (float)out_res;
   int r_lo, r_hi, tmp;
   float tl;
-  lin_src(Y0, k, sg, r_lo, tmp, tl);
-  lin_src(Y1 - 1, k, sg, tmp, r_hi, tl);
+  lin_idx(Y0, k, sg, r_lo, tmp, tl);
+  lin_idx(Y1 - 1, k, sg, tmp, r_hi, tl);
   const int nr = r_hi - r_lo + 1;
   const int64_t plane = (int64_t)h * w;
   const float* gp = lg + ((n * L + L - 1) * T + t) * plane;
@@ -218,21 +212,21 @@ __global__ __launch_bounds__(256) void sliding_merge_band_kernel(const float* __
   for (int X = threadIdx.x; X < out_res; X += blockDim.x) {
     int gx0, gx1;
     float glx;
-    lin_src(X, k, sg, gx0, gx1, glx);
+    lin_idx(X, k, sg, gx0, gx1, glx);
     int tx0[4], tx1[4], tbj[4];
     float tlx[4];
     int ncol = 0;
     for (int bj = 0; bj < nb && ncol < 4; ++bj) {
       const int xx = X - stride * bj;
       if (xx < 0 || xx >= k) continue;
-      lin_src(xx, w, (float)w / (float)k, tx0[ncol], tx1[ncol], tlx[ncol]);
+      lin_idx(xx, w, (float)w / (float)k, tx0[ncol], tx1[ncol], tlx[ncol]);
       tbj[ncol++] = bj;
     }
 #pragma unroll 4
     for (int Y = Y0; Y < Y1; ++Y) {       // unrolled: several rows' tile loads in flight
       int y0, y1;
       float ly;
-      lin_src(Y, k, sg, y0, y1, ly);
+      lin_idx(Y, k, sg, y0, y1, ly);
       const float* g0 = gsig + (y0 - r_lo) * k;
       const float* g1 = gsig + (y1 - r_lo) * k;
       const float glob = blend(g0[gx0], g0[gx1], g1[gx0], g1[gx1], ly, glx);
@@ -242,7 +236,7 @@ __global__ __launch_bounds__(256) void sliding_merge_band_kernel(const float* __
         if (yy < 0 || yy >= k) continue;
         int ty0, ty1;
         float tly;
-        lin_src(yy, h, (float)h / (float)k, ty0, ty1, tly);
+        lin_idx(yy, h, (float)h / (float)k, ty0, ty1, tly);
         for (int c = 0; c < ncol; ++c) {
           const float* pl = lg + ((n * L + bi * nb + tbj[c]) * T + t) * plane;
           sum += sigm_fast(blend(pl[ty0 * w + tx0[c]], pl[ty0 * w + tx1[c]], pl[ty1 * w + tx0[c]],
@@ -276,8 +270,8 @@ __global__ __launch_bounds__(256) void sliding_merge_stage_kernel(const float* _
   const float sg = (float)k / (float)out_res, st_ = (float)h / (float)k;
   int r_lo, r_hi, tmp;
   float tl;
-  lin_src(Y0, k, sg, r_lo, tmp, tl);
-  lin_src(Y1 - 1, k, sg, tmp, r_hi, tl);
+  lin_idx(Y0, k, sg, r_lo, tmp, tl);
+  lin_idx(Y1 - 1, k, sg, tmp, r_hi, tl);
   const int nr = r_hi - r_lo + 1;
   const int64_t plane = (int64_t)h * w;
   const float* gp = lg + ((n * L + L - 1) * T + t) * plane;
@@ -294,8 +288,8 @@ __global__ __launch_bounds__(256) void sliding_merge_stage_kernel(const float* _
     if (ya > yb) continue;
     int a0, a1, b0, b1;
     float la;
-    lin_src(ya - stride * bi, h, st_, a0, a1, la);
-    lin_src(yb - stride * bi, h, st_, b0, b1, la);
+    lin_idx(ya - stride * bi, h, st_, a0, a1, la);
+    lin_idx(yb - stride * bi, h, st_, b0, b1, la);
     tlo[bi] = a0;
     const int rows = b1 - a0 + 1;
     for (int bj = 0; bj < nb; ++bj) {
@@ -309,21 +303,21 @@ __global__ __launch_bounds__(256) void sliding_merge_stage_kernel(const float* _
   for (int X = threadIdx.x; X < out_res; X += blockDim.x) {
     int gx0, gx1;
     float glx;
-    lin_src(X, k, sg, gx0, gx1, glx);
+    lin_idx(X, k, sg, gx0, gx1, glx);
     int tx0[2], tx1[2], tbj[2];
     float tlx[2];
     int ncol = 0;
     for (int bj = 0; bj < nb && ncol < 2; ++bj) {
       const int xx = X - stride * bj;
       if (xx < 0 || xx >= k) continue;
-      lin_src(xx, w, (float)w / (float)k, tx0[ncol], tx1[ncol], tlx[ncol]);
+      lin_idx(xx, w, (float)w / (float)k, tx0[ncol], tx1[ncol], tlx[ncol]);
       tbj[ncol++] = bj;
     }
 #pragma unroll 4
     for (int Y = Y0; Y < Y1; ++Y) {
       int y0, y1;
       float ly;
-      lin_src(Y, k, sg, y0, y1, ly);
+      lin_idx(Y, k, sg, y0, y1, ly);
       const float* g0 = gsig + (y0 - r_lo) * k;
       const float* g1 = gsig + (y1 - r_lo) * k;
       const float glob = blend(g0[gx0], g0[gx1], g1[gx0], g1[gx1], ly, glx);
@@ -333,7 +327,7 @@ __global__ __launch_bounds__(256) void sliding_merge_stage_kernel(const float* _
         if (yy < 0 || yy >= k) continue;
         int ty0, ty1;
         float tly;
-        lin_src(yy, h, (float)h / (float)k, ty0, ty1, tly);
+        lin_idx(yy, h, (float)h / (float)k, ty0, ty1, tly);
         for (int c = 0; c < ncol; ++c) {
           const float* pl = tsl + (bi * 2 + tbj[c]) * trows * w - tlo[bi] * w;
           sum += sigm_fast(blend(pl[ty0 * w + tx0[c]], pl[ty0 * w + tx1[c]], pl[ty1 * w + tx0[c]],
@@ -347,7 +341,7 @@ __global__ __launch_bounds__(256) void sliding_merge_stage_kernel(const float* _
 }
 
 // The staged merge with the per-row interpolation terms tabulated once per workgroup (the row-side
-// lin_src of the global map and of both tile rows is uniform over a band row: computed per output
+// lin_idx of the global map and of both tile rows is uniform over a band row: computed per output
 // by every thread it was ~25 VALU of ~70) and the band's 16 x 640 outputs split evenly over the
 // threads (columns t and t + 256 for all rows, column 512 + t % 128 for half the rows: 40 each;
 // the column-per-thread walk gave 128 threads 48 outputs and 128 threads 32).  Same taps, blend,
@@ -376,16 +370,16 @@ __global__ __launch_bounds__(256) void sliding_merge_tab_kernel(const float* __r
   const float sg = (float)k / (float)out_res, st_ = (float)h / (float)k;
   int r_lo, r_hi, tmp;
   float tl;
-  lin_src(Y0, k, sg, r_lo, tmp, tl);
-  lin_src(Y1 - 1, k, sg, tmp, r_hi, tl);
+  lin_idx(Y0, k, sg, r_lo, tmp, tl);
+  lin_idx(Y1 - 1, k, sg, tmp, r_hi, tl);
   const int nr = r_hi - r_lo + 1;
   const int64_t plane = (int64_t)h * w;
   const float* gp = lg + ((n * L + L - 1) * T + t) * plane;
   int tlo[2] = {0, 0};
   {
     int gs_lo, gs_hi;
-    lin_src(r_lo, h, st_, gs_lo, tmp, tl);
-    lin_src(r_hi, h, st_, tmp, gs_hi, tl);
+    lin_idx(r_lo, h, st_, gs_lo, tmp, tl);
+    lin_idx(r_hi, h, st_, tmp, gs_hi, tl);
     const float* sp[5];
     float* sd[5];
     int se[5];                                 // cumulative segment ends of the flat copy list
@@ -399,8 +393,8 @@ __global__ __launch_bounds__(256) void sliding_merge_tab_kernel(const float* __r
       if (ya <= yb) {
         int a0, a1, b0, b1;
         float la;
-        lin_src(ya - stride * bi, h, st_, a0, a1, la);
-        lin_src(yb - stride * bi, h, st_, b0, b1, la);
+        lin_idx(ya - stride * bi, h, st_, a0, a1, la);
+        lin_idx(yb - stride * bi, h, st_, b0, b1, la);
         tlo[bi] = a0;
         rows = b1 - a0 + 1;
       }
@@ -436,11 +430,11 @@ __global__ __launch_bounds__(256) void sliding_merge_tab_kernel(const float* __r
       if (x < k) {
         int x0, x1;
         float lx;
-        lin_src(x, w, sx, x0, x1, lx);
+        lin_idx(x, w, sx, x0, x1, lx);
         for (int i = 0; i < nr; ++i) {
           int y0, y1;
           float ly;
-          lin_src(r_lo + i, h, st_, y0, y1, ly);
+          lin_idx(r_lo + i, h, st_, y0, y1, ly);
           const float* g0 = gsrc + (y0 - gs_lo) * w;
           const float* g1 = gsrc + (y1 - gs_lo) * w;
           gsig[i * k + x] = sigm_fast(blend(g0[x0], g0[x1], g1[x0], g1[x1], ly, lx));
@@ -452,7 +446,7 @@ __global__ __launch_bounds__(256) void sliding_merge_tab_kernel(const float* __r
     const int Y = Y0 + threadIdx.x;
     int y0, y1;
     float ly;
-    lin_src(Y, k, sg, y0, y1, ly);
+    lin_idx(Y, k, sg, y0, y1, ly);
     ti[threadIdx.x][0] = (y0 - r_lo) * k;
     ti[threadIdx.x][1] = (y1 - r_lo) * k;
     tf[threadIdx.x][0] = ly;
@@ -466,7 +460,7 @@ __global__ __launch_bounds__(256) void sliding_merge_tab_kernel(const float* __r
       } else {
         int ty0, ty1;
         float tly;
-        lin_src(yy, h, st_, ty0, ty1, tly);
+        lin_idx(yy, h, st_, ty0, ty1, tly);
         ti[threadIdx.x][2 + 2 * bi] = (ty0 - tlo[bi]) * w;
         ti[threadIdx.x][3 + 2 * bi] = (ty1 - tlo[bi]) * w;
         tf[threadIdx.x][1 + bi] = tly;
@@ -500,7 +494,7 @@ __global__ __launch_bounds__(256) void sliding_merge_tab_kernel(const float* __r
     }
     int gx0, gx1;
     float glx;
-    lin_src(X, k, sg, gx0, gx1, glx);
+    lin_idx(X, k, sg, gx0, gx1, glx);
     int tx0[2], tx1[2], tbj[2];
     float tlx[2];
     int ncol = 0;
@@ -508,7 +502,7 @@ __global__ __launch_bounds__(256) void sliding_merge_tab_kernel(const float* __r
     for (int bj = 0; bj < nb; ++bj) {
       const int xx = X - stride * bj;
       if (xx < 0 || xx >= k) continue;
-      lin_src(xx, w, (float)w / (float)k, tx0[ncol], tx1[ncol], tlx[ncol]);
+      lin_idx(xx, w, (float)w / (float)k, tx0[ncol], tx1[ncol], tlx[ncol]);
       tbj[ncol++] = bj;
     }
     // branch-light form: the second tile column duplicates the first's taps with weight 0 where

@@ -65,6 +65,11 @@ EXACT = [  # B, T, h, w, crop, H, W
     # the source patch of a tile is 8 x 32 = 256 floats: the last size served by the 16-classes-per-chunk
     # kernel; 18 classes: a second chunk that runs past T
     pytest.param(1, 18, 16, 32, None, 60, 72, id="patch-256"),
+    # larger patches: 8 passes of 256 elements (two classes per chunk, read as pairs), 16 passes (one class
+    # per chunk, scalar reads), and the 64 x 64 = 4096-float patch that is the last to fit the LDS stage
+    pytest.param(1, 5, 40, 54, None, 20, 72, id="npp8"),
+    pytest.param(1, 3, 60, 72, None, 20, 72, id="npp16"),
+    pytest.param(1, 2, 64, 64, None, 16, 64, id="patch-4096"),
 ]
 
 
@@ -81,10 +86,16 @@ def test_equals_argmax_of_postprocess(B, T, h, w, crop, H, W):
         assert 0 < (ref_l > 0).float().mean() < 1
 
 
-@pytest.mark.parametrize("H,W", [(30, 44), (40, 40)])
-def test_equals_argmax_of_resize_bilinear(H, W):
-    assert _banded(40, 40, H, W)
-    lg = _levels((1, 33, 40, 40), seed=H)
+@pytest.mark.parametrize("T,h,w,H,W", [
+    pytest.param(33, 40, 40, 30, 44, id="30-44"),
+    pytest.param(33, 40, 40, 40, 40, id="40-40"),
+    pytest.param(5, 40, 54, 20, 72, id="npp8"),
+    pytest.param(3, 60, 72, 20, 72, id="npp16"),
+    pytest.param(2, 64, 64, 16, 64, id="patch-4096"),
+])
+def test_equals_argmax_of_resize_bilinear(T, h, w, H, W):
+    assert _banded(h, w, H, W)
+    lg = _levels((1, T, h, w), seed=H)
     ref_l, ref_s = _existing(lg, H, W, None, False)
     lab, sc = _fused(lg, H, W, None, False)
     assert torch.equal(lab, ref_l)
@@ -113,6 +124,28 @@ def test_nan_ranks_highest_first_nan_wins(sigmoid):
     assert torch.allclose(sc, ref_s, rtol=0, atol=0, equal_nan=True)
 
 
+@pytest.mark.parametrize("sigmoid", [True, False])
+def test_nan_one_class_per_chunk(sigmoid):
+    """The same planted values at 60 x 72 -> 20 x 72, where a chunk holds one class: output row y reads
+    source row 3 y + 1 with weight 1 (and row 3 y + 2 with weight 0), output column x reads column x, so
+    the values planted in source row 3 r + 1 reach output row r as they are."""
+    lg = _levels((1, 9, 60, 72), seed=7)
+    lg[0, 3, 1, :5] = float("nan")         # NaN at a class index > 0
+    lg[0, 5, 4, :] = float("nan")
+    lg[0, 2, 4, ::2] = float("nan")        # two NaNs at one pixel: the first (class 2) wins
+    lg[0, 0, 7, :3] = float("nan")         # NaN at class 0
+    lg[0, 7, 10, 4] = float("inf")
+    lg[0, 8, 10, 4] = float("nan")         # NaN after +inf at one pixel
+    lg[0, 6, 16, 6] = float("inf")         # +inf alone
+    assert _banded(60, 72, 20, 72)
+    ref_l, ref_s = _existing(lg, 20, 72, None, sigmoid)
+    lab, sc = _fused(lg, 20, 72, None, sigmoid)
+    assert int(ref_l[0, 2, 0]) == 0 and int(ref_l[0, 1, 0]) == 2 and int(ref_l[0, 1, 71]) == 5
+    assert torch.equal(lab, ref_l)
+    assert torch.equal(sc.isnan(), ref_s.isnan()) and int(sc.isnan().sum()) >= 5 + 72 + 3 + 1
+    assert torch.allclose(sc, ref_s, rtol=0, atol=0, equal_nan=True)
+
+
 # ---------------------------------------------------------------- D: widths the existing kernel does not band
 FP64 = [  # T, h, w, crop, H, W, sigmoid
     pytest.param(7, 24, 24, (20, 23), 50, 67, True, id="odd-width-cropped"),
@@ -120,6 +153,11 @@ FP64 = [  # T, h, w, crop, H, W, sigmoid
     pytest.param(19, 24, 24, None, 17, 19, True, id="downsample"),
     pytest.param(33, 40, 40, None, 30, 42, False, id="no-sigmoid"),
     pytest.param(847, 24, 24, None, 61, 45, True, id="T847"),
+    # two classes per chunk (8 passes over the patch) and one (16 passes), at an odd width
+    pytest.param(5, 40, 54, None, 19, 70, True, id="npp8"),
+    pytest.param(5, 40, 54, None, 19, 70, False, id="npp8-no-sigmoid"),
+    pytest.param(3, 60, 72, None, 19, 70, True, id="npp16"),
+    pytest.param(3, 60, 72, None, 19, 70, False, id="npp16-no-sigmoid"),
 ]
 
 

@@ -73,6 +73,11 @@ EXACT = [  # K, T, h, w, crops, flips, H, W
     pytest.param(2, 19, 40, 40, None, [1, 0], 28, 36, id="downsample"),
     pytest.param(18, 150, 96, 96, [(96, 96)] * 16 + [(96, 72), (80, 96)], None, 128, 172, id="K18-T150"),
     pytest.param(32, 3, 8, 8, None, None, 32, 32, id="K32"),
+    # larger patches: 8 passes of 256 elements (two classes per chunk, read as pairs), 16 passes (one class
+    # per chunk, scalar reads), and the 64 x 64 = 4096-float patch that is the last to fit the LDS stage
+    pytest.param(3, 5, 40, 54, [(40, 54), (33, 54), (40, 41)], [1, 0, 1], 20, 72, id="npp8"),
+    pytest.param(2, 3, 60, 72, None, [0, 1], 20, 72, id="npp16"),
+    pytest.param(1, 2, 64, 64, [(64, 64)], [0], 16, 64, id="patch-4096"),
 ]
 
 
@@ -104,6 +109,8 @@ FP64 = [  # K, T, h, w, crops, flips, H, W
     pytest.param(3, 7, 24, 24, [(20, 23), (24, 24), (12, 17)], [1, 0, 1], 50, 67, id="odd-width-cropped"),
     pytest.param(6, 847, 24, 24, [(24, 24), (20, 23)] * 3, None, 61, 45, id="T847"),
     pytest.param(5, 19, 40, 40, None, None, 17, 19, id="downsample"),
+    pytest.param(3, 5, 40, 54, None, [1, 0, 1], 19, 70, id="npp8"),
+    pytest.param(3, 3, 60, 72, None, [0, 1, 1], 19, 70, id="npp16"),
 ]
 
 
