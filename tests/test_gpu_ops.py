@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import poison
 from cat_seg import ops
 from cat_seg import _lib as L
 from cat_seg._lib import rowmap
@@ -21,9 +22,21 @@ def rnd(*shape, seed=0, scale=1.0):
     return (torch.rand(*shape, generator=g) * 2 - 1) * scale
 
 
+def nan_out(*shape, device=dev, dtype=torch.float32):
+    """An output its call is documented to overwrite completely, prefilled with NaN (fp8: the NaN byte;
+    integers: a negative pattern no kernel here produces), so that an element the kernel leaves unwritten
+    cannot pass on what an earlier test left in the allocator's block."""
+    return poison.filled(tuple(shape), dtype, device)
+
+
+def nan_like(t):
+    return poison.filled(tuple(t.shape), t.dtype, t.device)
+
+
 def close(got, ref, atol, rtol=0.0, what=""):
     got = got.float().cpu()
     ref = ref.float().cpu()
+    assert not torch.isnan(got).any(), f"{what}: {int(torch.isnan(got).sum())} NaN element(s) in the result"
     err = (got - ref).abs().max().item()
     tol = atol + rtol * ref.abs().max().item()
     assert err <= tol, f"{what}: max abs err {err:.3e} > {tol:.3e}"
@@ -41,7 +54,7 @@ def test_gemm_plain(dt, M, N, K):
     A = rnd(M, K, seed=1)
     W = rnd(N, K, seed=2) / math.sqrt(K)
     b = rnd(N, seed=3)
-    out = torch.empty(M, N, device=dev, dtype=torch.float32)
+    out = nan_out(M, N, device=dev, dtype=torch.float32)
     ops.gemm(A.to(dev, dt), W.to(dev, dt), out, bias=b.to(dev))
     ref = A.to(dt).double() @ W.to(dt).double().T + b.double()
     close(out, ref, atol=2e-5 if dt == torch.float32 else 1e-3, what="gemm")
@@ -60,7 +73,7 @@ def test_gemm_epilogues(dt):
     gmap = rowmap(d1=3 * 20, s1=20, d2=1, m2=20, s2=1)
     outs = {}
     for act in (L.ACT_NONE, L.ACT_RELU, L.ACT_GELU, L.ACT_QUICKGELU):
-        out = torch.empty(M, N, device=dev, dtype=dt)
+        out = nan_out(M, N, device=dev, dtype=dt)
         ops.gemm(A.to(dev, dt), W.to(dev, dt), out, bias=b.to(dev), act=act, add=add.to(dev, dt), addmap=gmap,
                  add_ncols=256, res=res.to(dev, dt), res2=res2.to(dev, dt), amap=amap)
         v = A.to(dt).double() @ W.to(dt).double().T + b.double()
@@ -83,7 +96,7 @@ def test_gemm_convtranspose_store(dt):
     ref = F.conv_transpose2d(x.to(dt).double(), w.to(dt).double(), b.double(), stride=k)   # (S, cout, kH, kW)
     A = x.permute(0, 2, 3, 1).reshape(S * H * Wd, cin)
     Wg = w.permute(2, 3, 1, 0).reshape(k * k * cout, cin)
-    out = torch.empty(S * H * k * Wd * k, cout, device=dev, dtype=dt)
+    out = nan_out(S * H * k * Wd * k, cout, device=dev, dtype=dt)
     ops.gemm(A.to(dev, dt).contiguous(), Wg.to(dev, dt).contiguous(), out, bias=b.repeat(k * k).to(dev),
              store=(k, H, Wd, cout))
     got = out.reshape(S, H * k, Wd * k, cout).permute(0, 3, 1, 2)
@@ -192,8 +205,8 @@ def test_quant_fp8_rows_bit_exact(dt, rows, cols):
     if rows > 2:
         x[2] = 0.0
     x = x.to(dt)
-    q = torch.empty(rows, cols, device=dev, dtype=torch.float8_e4m3fn)
-    sc = torch.empty(rows, device=dev, dtype=torch.float32)
+    q = nan_out(rows, cols, device=dev, dtype=torch.float8_e4m3fn)
+    sc = nan_out(rows, device=dev, dtype=torch.float32)
     ops.quant_fp8_rows(x.to(dev), q, sc)
     qr, sr = _quant_ref(x)
     assert torch.equal(sc.cpu(), sr), (sc.cpu() - sr).abs().max()
@@ -210,8 +223,8 @@ def test_layernorm_fp8(dt):
     b = rnd(C, seed=82) * 0.1
     M = B * (L_ - 1)
     amap = rowmap(d1=L_ - 1, s1=L_, d2=1, m2=L_ - 1, s2=1, off=1)
-    q = torch.empty(M, C, device=dev, dtype=torch.float8_e4m3fn)
-    sc = torch.empty(M, device=dev)
+    q = nan_out(M, C, device=dev, dtype=torch.float8_e4m3fn)
+    sc = nan_out(M, device=dev)
     ops.layernorm_fp8(x.to(dev, dt), g.to(dev), b.to(dev), q, sc, rows=M, inmap=amap)
     xr = x.to(dt).double().reshape(B, L_, C)[:, 1:].reshape(-1, C)
     ln = F.layer_norm(xr, (C,), g.double(), b.double(), eps=1e-5)
@@ -299,13 +312,13 @@ def test_gemm_fp8_vit_shapes_vs_bf16():
     for N, K in ((3072, 1024), (1024, 1024), (4096, 1024), (1024, 4096)):
         A = rnd(M, K, seed=N + K)
         W = rnd(N, K, seed=N + K + 1) / math.sqrt(K)
-        qa = torch.empty(M, K, device=dev, dtype=torch.float8_e4m3fn)
-        sa = torch.empty(M, device=dev)
-        qw = torch.empty(N, K, device=dev, dtype=torch.float8_e4m3fn)
-        sw = torch.empty(N, device=dev)
+        qa = nan_out(M, K, device=dev, dtype=torch.float8_e4m3fn)
+        sa = nan_out(M, device=dev)
+        qw = nan_out(N, K, device=dev, dtype=torch.float8_e4m3fn)
+        sw = nan_out(N, device=dev)
         ops.quant_fp8_rows(A.to(dev, torch.bfloat16), qa, sa)
         ops.quant_fp8_rows(W.to(dev), qw, sw)
-        out = torch.empty(M, N, device=dev)
+        out = nan_out(M, N, device=dev)
         ops.gemm_fp8(qa, sa, qw, sw, out)
         ref = (qa.cpu().double() * sa.cpu().double()[:, None]) @ (qw.cpu().double() * sw.cpu().double()[:, None]).T
         close(out, ref, atol=1e-4, what=f"gemm_fp8 {M}x{N}x{K}")
@@ -318,7 +331,7 @@ def test_gemm_amap_cls_drop():
     B, L_, C = 2, 5, 16
     A = rnd(B * L_, C, seed=13)
     W = rnd(8, C, seed=14)
-    out = torch.empty(B * (L_ - 1), 8, device=dev)
+    out = nan_out(B * (L_ - 1), 8, device=dev)
     ops.gemm(A.to(dev), W.to(dev), out, M=B * (L_ - 1), amap=rowmap(d1=L_ - 1, s1=L_, d2=1, m2=L_ - 1, s2=1, off=1))
     ref = A.reshape(B, L_, C)[:, 1:].reshape(-1, C).double() @ W.double().T
     close(out, ref, atol=1e-5, what="amap")
@@ -330,10 +343,11 @@ def test_gemm_amap_cls_drop():
 def test_layernorm_l2(cols, dt):
     x = rnd(77, cols, seed=15) * 3 + 0.5
     g, b = rnd(cols, seed=16) + 1, rnd(cols, seed=17)
-    out = torch.empty(77, cols, device=dev, dtype=dt)
+    out = nan_out(77, cols, device=dev, dtype=dt)
     ops.layernorm(x.to(dev), g.to(dev), b.to(dev), out)
     close(out, F.layer_norm(x.double(), (cols,), g.double(), b.double(), 1e-5),
           atol=2e-5 if dt == torch.float32 else 2e-2, what="LN")
+    out = nan_like(out)
     ops.l2normalize(x.to(dev), out)
     close(out, F.normalize(x.double(), dim=-1), atol=1e-6 if dt == torch.float32 else 4e-3, what="l2")
 
@@ -351,7 +365,7 @@ def test_layernorm_pipelined_rows(rows):
     outs = []
     for v in (0, 1):
         L.tune("ln_variant", v)
-        o = torch.empty(rows, cols, device=dev, dtype=torch.bfloat16)
+        o = nan_out(rows, cols, device=dev, dtype=torch.bfloat16)
         ops.layernorm(x.to(dev), g.to(dev), b.to(dev), o)
         outs.append(o)
     L.tune("ln_variant", 0)
@@ -367,7 +381,7 @@ def test_layernorm_pipelined_rows(rows):
 def test_attention_dense(dt, L_, H, causal):
     B, d = 2, 64
     qkv = rnd(B * L_, 3 * H * d, seed=18) * 2
-    out = torch.empty(B * L_, H * d, device=dev, dtype=dt)
+    out = nan_out(B * L_, H * d, device=dev, dtype=dt)
     q = qkv.to(dev, dt)
     ops.attention(q[:, :H * d], q[:, H * d:2 * H * d], q[:, 2 * H * d:], out, n_seq=B, seq_len=L_, n_heads=H,
                   head_dim=d, scale=d ** -0.5, causal=causal)
@@ -392,7 +406,7 @@ def test_attention_dense_log2_scaled_q(L_, spike):
     q = qkv.clone()
     q[:, :H * d] *= c
     qb = q.to(dev, torch.bfloat16)
-    out = torch.empty(B * L_, H * d, device=dev, dtype=torch.bfloat16)
+    out = nan_out(B * L_, H * d, device=dev, dtype=torch.bfloat16)
     ops.attention(qb[:, :H * d], qb[:, H * d:2 * H * d], qb[:, 2 * H * d:], out, n_seq=B, seq_len=L_,
                   n_heads=H, head_dim=d, scale=0.0, mode=2)
     x = q.to(torch.bfloat16).double().reshape(B, L_, 3, H, d).permute(2, 0, 3, 1, 4)
@@ -411,12 +425,12 @@ def test_attention_dense_tilings(variant):
     q = (rnd(B * L_, 3 * H * d, seed=19) * 2).to(dev, torch.bfloat16)
     args = (q[:, :H * d], q[:, H * d:2 * H * d], q[:, 2 * H * d:])
     kw = dict(n_seq=B, seq_len=L_, n_heads=H, head_dim=d, scale=d ** -0.5)
-    ref = torch.empty(B * L_, H * d, device=dev, dtype=torch.bfloat16)
+    ref = nan_out(B * L_, H * d, device=dev, dtype=torch.bfloat16)
     ops.attention(*args, ref, **kw)
     lib = L.load()
     try:
         L.tune("attn_variant", variant)
-        out = torch.empty_like(ref)
+        out = nan_like(ref)
         ops.attention(*args, out, **kw)
     finally:
         L.tune("attn_variant", 0)
@@ -436,7 +450,7 @@ def test_attention_dense_defer_max_rescale(spike_key):
     for qrow in (3, 200, 576):                        # k[spike] ~ 12 * q[qrow] for head 0 only
         qkv[spike_key, H * d:H * d + d] += 12 * qkv[qrow, :d] / 3
     q = qkv.to(dev, torch.bfloat16)
-    out = torch.empty(B * L_, H * d, device=dev, dtype=torch.bfloat16)
+    out = nan_out(B * L_, H * d, device=dev, dtype=torch.bfloat16)
     ops.attention(q[:, :H * d], q[:, k_cols], q[:, 2 * H * d:], out, n_seq=B, seq_len=L_, n_heads=H,
                   head_dim=d, scale=d ** -0.5)
     x = qkv.to(torch.bfloat16).double().reshape(B, L_, 3, H, d).permute(2, 0, 3, 1, 4)
@@ -445,7 +459,7 @@ def test_attention_dense_defer_max_rescale(spike_key):
         assert s[0, 0].max(-1).values.max() - s[0, 0, :, :64].max() > 30
     ref = (torch.softmax(s, -1) @ x[2]).permute(0, 2, 1, 3).reshape(B * L_, H * d)
     close(out, ref, atol=1.5e-2, what=f"attn defer-max spike at key {spike_key}")
-    alt = torch.empty_like(out)
+    alt = nan_like(out)
     try:
         L.tune("attn_variant", 7)                     # the exact-max kernel (rescales every block)
         ops.attention(q[:, :H * d], q[:, k_cols], q[:, 2 * H * d:], alt, n_seq=B, seq_len=L_, n_heads=H,
@@ -461,7 +475,7 @@ def test_attention_swin_windows(dt, shift):
     S, Hh, Ww, ws, nh, hd = 3, 24, 24, 12, 4, 32
     D = nh * hd
     qkv = rnd(S * Hh * Ww, 3 * D, seed=19) * 2
-    out = torch.empty(S * Hh * Ww, D, device=dev, dtype=dt)
+    out = nan_out(S * Hh * Ww, D, device=dev, dtype=dt)
     q = qkv.to(dev, dt)
     ops.attention(q[:, :D], q[:, D:2 * D], q[:, 2 * D:], out, n_seq=S * 4, seq_len=ws * ws, n_heads=nh,
                   head_dim=hd, scale=hd ** -0.5, mode=1, img_hw=(Hh, Ww), window=ws, shift=shift)
@@ -490,7 +504,7 @@ def test_linear_attention(dt, T, n_pad):
     x = rnd(B * T * HW, D, seed=21)
     kp, vp = rnd(D, seed=22), rnd(D, seed=23)
     qd, xd = qkv.to(dev, dt), x.to(dev, dt)
-    y = torch.empty_like(xd)
+    y = nan_like(xd)
     ops.linear_attention(qd[:, :D], qd[:, D:2 * D], qd[:, 2 * D:], xd, y, B=B, T=T, HW=HW, n_heads=4, head_dim=32,
                          n_pad=n_pad, k_pad=kp.to(dev), v_pad=vp.to(dev))
     z = qkv.to(dt).double().reshape(B, T, HW, 3, 4, 32).permute(3, 0, 2, 1, 4, 5).reshape(3, B * HW, T, 4, 32)
@@ -513,7 +527,7 @@ def test_full_class_attention(dt, T, n_pad):
     x = rnd(B * T * HW, D, seed=25)
     kp, vp = rnd(D, seed=26), rnd(D, seed=27)
     qd, xd = qkv.to(dev, dt), x.to(dev, dt)
-    y = torch.empty_like(xd)
+    y = nan_like(xd)
     ops.full_attention(qd, xd, y, B=B, T=T, HW=HW, n_heads=4, head_dim=32, n_pad=n_pad, k_pad=kp.to(dev),
                        v_pad=vp.to(dev))
     z = qkv.to(dt).double().reshape(B, T, HW, 3, 4, 32).permute(3, 0, 2, 1, 4, 5).reshape(3, B * HW, T, 4, 32)
@@ -542,7 +556,7 @@ def test_class_attention_fused(T, n_pad, per_image):
     ntg = B * T if per_image else T
     tg = rnd(ntg, 2 * D, seed=66, scale=0.5).to(dev, dt)
     kp, vp = rnd(D, seed=67).to(dev), rnd(D, seed=68).to(dev)
-    y = torch.empty_like(X)
+    y = nan_like(X)
     ops.class_attention(X, (g1, b1), W, bias, tg, y, B=B, T=T, HW=HW, n_heads=4, head_dim=32,
                         tg_bstride=T if per_image else 0, n_pad=n_pad, k_pad=kp, v_pad=vp)
     # fp64 restatement on the same bf16 inputs
@@ -565,16 +579,16 @@ def test_class_attention_fused(T, n_pad, per_image):
     err = (y.double().cpu() - ref).abs()
     assert err.max().item() < 5e-2 and err.mean().item() < 5e-3, (err.max().item(), err.mean().item())
     # the unfused bf16 pair (q/k/v rounded to bf16 in HBM) on the same inputs
-    qkv_d = torch.empty(R, 3 * D, device=dev, dtype=dt)
+    qkv_d = nan_out(R, 3 * D, device=dev, dtype=dt)
     tmap = rowmap(d1=HW) if per_image else rowmap(d1=HW, m1=T)
     ops.rows_gemm(X, W, qkv_d, ln=(g1, b1), bias=bias, add=tg, addmap=tmap, add_ncols=2 * D)
-    y2 = torch.empty_like(X)
+    y2 = nan_like(X)
     ops.linear_attention(qkv_d[:, :D], qkv_d[:, D:2 * D], qkv_d[:, 2 * D:], X, y2, B=B, T=T, HW=HW, n_heads=4,
                          head_dim=32, n_pad=n_pad, k_pad=kp, v_pad=vp)
     e2 = (y.float() - y2.float()).abs()
     assert e2.max().item() < 5e-2 and e2.mean().item() < 5e-3, (e2.max().item(), e2.mean().item())
     # a second launch computes the same bits (no atomics, fixed reduction order)
-    y3 = torch.empty_like(X)
+    y3 = nan_like(X)
     ops.class_attention(X, (g1, b1), W, bias, tg, y3, B=B, T=T, HW=HW, n_heads=4, head_dim=32,
                         tg_bstride=T if per_image else 0, n_pad=n_pad, k_pad=kp, v_pad=vp)
     torch.cuda.synchronize()
@@ -594,15 +608,15 @@ def test_conv3x3_dual_source_gn(dt):
     a1 = x1.permute(0, 2, 3, 1).contiguous().to(dev, dt)
     a2 = x2.permute(0, 2, 3, 1).contiguous().to(dev, dt)
     wk = w.permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev, dt)
-    out = torch.empty(S * H * W, co, device=dev, dtype=dt)
+    out = nan_out(S * H * W, co, device=dev, dtype=dt)
     tiles = H * W // ops.conv_tile_rows()
-    st = torch.empty(S * tiles * (co // 16) * 2, device=dev)
+    st = nan_out(S * tiles * (co // 16) * 2, device=dev)
     ops.conv3x3(a1, wk, out, S=S, H=H, W=W, c1=c1, src2=a2, c2=c2, src2_div=T, stats=st)
     got = out.reshape(S, H, W, co).permute(0, 3, 1, 2)
     tol = 1e-5 if dt == torch.float32 else 3e-2
     close(got, ref, atol=tol, what="conv")
-    mean = torch.empty(S * (co // 16), device=dev)
-    rstd = torch.empty_like(mean)
+    mean = nan_out(S * (co // 16), device=dev)
+    rstd = nan_like(mean)
     ops.groupnorm_stats(st, S, tiles, co // 16, ops.conv_tile_rows() * 16, mean, rstd)
     g = ref.reshape(S, co // 16, -1)
     close(mean, g.mean(-1).reshape(-1), atol=1e-5 if dt == torch.float32 else 1e-3, what="gn mean")
@@ -613,12 +627,12 @@ def test_conv3x3_dual_source_gn(dt):
     w2 = rnd(co, co, 3, 3, seed=29) / 8
     y1 = F.relu(F.group_norm(ref, co // 16, gam.double(), bet.double(), 1e-5))
     ref2 = F.conv2d(y1, w2.to(dt).double(), padding=1)
-    out2 = torch.empty_like(out)
+    out2 = nan_like(out)
     ops.conv3x3(out, w2.permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev, dt), out2, S=S, H=H, W=W, c1=co,
                 gn=(mean, rstd, gam.to(dev), bet.to(dev), 16))
     close(out2.reshape(S, H, W, co).permute(0, 3, 1, 2), ref2, atol=1e-4 if dt == torch.float32 else 8e-2,
           what="conv gn prologue")
-    z = torch.empty_like(out)
+    z = nan_like(out)
     ops.groupnorm_relu(out, z, S=S, HW=H * W, C=co, cpg=16, mean=mean, rstd=rstd, gamma=gam.to(dev), beta=bet.to(dev))
     close(z.reshape(S, H, W, co).permute(0, 3, 1, 2), y1, atol=1e-4 if dt == torch.float32 else 2e-2,
           rtol=0 if dt == torch.float32 else 1e-2, what="gn relu")
@@ -646,7 +660,7 @@ def test_conv3x3_splitk_guidance_projection(dt, S, H, c1, co):
     ref = F.relu(F.conv2d(x.to(dt).double(), w.to(dt).double(), b.double(), padding=1))
     xd = x.permute(0, 2, 3, 1).contiguous().to(dev, dt)
     wk = w.permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev, dt)
-    out = torch.empty(S * H * H, co, device=dev, dtype=dt)
+    out = nan_out(S * H * H, co, device=dev, dtype=dt)
     a = ops._conv_args(xd, wk, out, S, H, H, c1, None, 0, None, 0, 0, 0, 1, b.to(dev), L.ACT_RELU, None, None, 16,
                        None, 1)
     assert lib.catseg_conv3x3_workspace(ops.C.byref(a)) > 0      # these shapes do split
@@ -670,12 +684,12 @@ def test_conv3x3_ring_guidance_split(c1, c2, co, H):
     xin = torch.cat([x1, x2.repeat_interleave(T, 0)], 1) if c2 else x1
     ref = F.conv2d(xin.to(dt).double(), w.to(dt).double(), padding=1)
     a1 = x1.permute(0, 2, 3, 1).contiguous().to(dev, dt)
-    out = torch.empty(S * H * W, co, device=dev, dtype=dt)
+    out = nan_out(S * H * W, co, device=dev, dtype=dt)
     if c2:
         a2 = x2.permute(0, 2, 3, 1).contiguous().to(dev, dt)
         wx = w[:, :c1].permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev, dt)
         wg = w[:, c1:].to(dt).float().permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev)
-        part = torch.empty(B * H * W, co, device=dev)
+        part = nan_out(B * H * W, co, device=dev)
         ops.conv3x3_partial(a2, wg, part, B=B, H=H, W=W)
         refp = F.conv2d(x2.to(dt).double(), w[:, c1:].to(dt).double(), padding=1)
         close(part.reshape(B, H, W, co).permute(0, 3, 1, 2), refp, atol=1e-4, what="partial conv")
@@ -684,14 +698,14 @@ def test_conv3x3_ring_guidance_split(c1, c2, co, H):
         kw, wc = dict(S=S, H=H, W=W, c1=c1), w.permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev, dt)
     tile = ops.conv3x3_stats_tile(a1, wc, **kw)
     tiles = H * W // tile
-    st = torch.empty(S * tiles * (co // 16) * 2, device=dev)
+    st = nan_out(S * tiles * (co // 16) * 2, device=dev)
     ops.conv3x3(a1, wc, out, stats=st, **kw)
     got = out.reshape(S, H, W, co).permute(0, 3, 1, 2).double().cpu()
     err = (got - ref).abs() - 2.0 ** -8 * ref.abs()
     assert err.max().item() <= 1e-5, err.max().item()
     # the one-barrier-per-chunk rings (tuning knob ring_onebar 1, default) equal the two-barrier form bit for bit
     L.load()
-    out1, st1 = torch.empty_like(out), torch.empty_like(st)
+    out1, st1 = nan_like(out), nan_like(st)
     try:
         L.tune("ring_onebar", 0)
         ops.conv3x3(a1, wc, out1, stats=st1, **kw)
@@ -699,15 +713,15 @@ def test_conv3x3_ring_guidance_split(c1, c2, co, H):
     finally:
         L.tune("ring_onebar", 1)
     assert torch.equal(out1, out) and torch.equal(st1, st)
-    mean = torch.empty(S * (co // 16), device=dev)
-    rstd = torch.empty_like(mean)
+    mean = nan_out(S * (co // 16), device=dev)
+    rstd = nan_like(mean)
     ops.groupnorm_stats(st, S, tiles, co // 16, tile * 16, mean, rstd)
     g = ref.reshape(S, co // 16, -1)
     close(mean, g.mean(-1).reshape(-1), atol=1e-4, what="gn mean")
     close(rstd, (1 / torch.sqrt(g.var(-1, unbiased=False) + 1e-5)).reshape(-1), atol=0, rtol=2e-3, what="gn rstd")
     if c2:
         # the unsplit path (guidance channels read per class) on the same inputs
-        out2 = torch.empty_like(out)
+        out2 = nan_like(out)
         wk = w.permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev, dt)
         ops.conv3x3(a1, wk, out2, S=S, H=H, W=W, c1=c1, src2=a2, c2=c2, src2_div=T)
         e2 = (out.float() - out2.float()).abs() - 2.0 ** -7 * out2.float().abs()   # one bf16 rounding apart
@@ -722,13 +736,13 @@ def test_corr_embed_topk(dt):
     w = rnd(hid, 1, 7, 7, seed=32) / 7
     b = rnd(hid, seed=33)
     k = 16
-    cls = torch.empty(B, k, device=dev, dtype=torch.int32)
+    cls = nan_out(B, k, device=dev, dtype=torch.int32)
     cd = corr.to(dev)
     ops.topk_classes(cd, t_stride=B * H * W, b_stride=H * W, B=B, T=T, HW=H * W, k=k, out=cls)
     m = corr.reshape(T, B, H * W).max(-1)[0].T   # (B, T)
     ref_cls = m.topk(k, -1)[1]
     assert torch.equal(torch.sort(cls.cpu().long(), -1)[0], torch.sort(ref_cls, -1)[0])
-    X = torch.empty(B * k * H * W, hid, device=dev, dtype=dt)
+    X = nan_out(B * k * H * W, hid, device=dev, dtype=dt)
     ops.corr_embed(cd, t_stride=B * H * W, b_stride=H * W, B=B, T=k, H=H, W=W, weight=w.reshape(hid, 49).to(dev),
                    bias=b.to(dev), out=X, classes=cls)
     c = corr.reshape(T, B, H, W).permute(1, 0, 2, 3)
@@ -762,7 +776,7 @@ def test_topk_classes_exact(B, T, HW, k):
     c3 = corr.reshape(T, B, HW)
     c3[10:20, :, 5] = 7.0                   # ten classes tie at the top in every image
     c3[30:34, :, :] = -3.0                  # and four tie at a constant row
-    cls = torch.empty(B, k, device=dev, dtype=torch.int32)
+    cls = nan_out(B, k, device=dev, dtype=torch.int32)
     ops.topk_classes(corr.to(dev), t_stride=B * HW, b_stride=HW, B=B, T=T, HW=HW, k=k, out=cls)
     m = c3.max(-1)[0].T                     # (B, T)
     for b in range(B):
@@ -787,7 +801,7 @@ def test_preprocess_im2col(p, res):
     for i, im in enumerate(imgs):
         raw[i, :, :im.shape[1], :im.shape[2]] = im
     G = res // p
-    out = torch.empty(2 * G * G, 3 * p * p + 32, device=dev)
+    out = nan_out(2 * G * G, 3 * p * p + 32, device=dev)
     ops.preprocess_im2col(raw.to(dev), torch.tensor(sizes, dtype=torch.int32).to(dev), mean=arch_mean.to(dev),
                           std=arch_std.to(dev), res=res, patch=p, out=out)
     cols = F.unfold(ref, p, stride=p).transpose(1, 2).reshape(-1, 3 * p * p)
@@ -798,13 +812,13 @@ def test_preprocess_im2col(p, res):
 def test_bicubic_postprocess():
     S_in, S_out, D = 14, 24, 8
     g = rnd(S_in * S_in, D, seed=34)
-    out = torch.empty(S_out * S_out, D, device=dev)
+    out = nan_out(S_out * S_out, D, device=dev)
     ops.bicubic_resize(g.to(dev), S_in, D, out, S_out)
     pos = torch.cat([torch.zeros(1, D), g], 0)
     ref = O.resized_pos_embed(pos, S_in, S_out)[1:]
     close(out, ref, atol=2e-6, what="bicubic")
     lg = rnd(2, 3, 96, 96, seed=35) * 4
-    o = torch.empty(2, 3, 333, 250, device=dev)
+    o = nan_out(2, 3, 333, 250, device=dev)
     ops.postprocess(lg.to(dev), o)
     ref = F.interpolate(lg.sigmoid(), size=(333, 250), mode="bilinear", align_corners=False)
     close(o, ref, atol=2e-6, what="postprocess")
@@ -821,7 +835,7 @@ def test_postprocess_compile_time_width(HW, crop):
     try:
         for v in (0, 1):
             L.tune("post_variant", v)
-            o = torch.empty(2, 5, HW, HW, device=dev)
+            o = nan_out(2, 5, HW, HW, device=dev)
             if crop is None:
                 ops.postprocess(lg, o)
             else:
@@ -854,7 +868,7 @@ def test_rows_gemm_ln_add_res_and_convt(dt, M, rows_variant):
     add = rnd(M // 10 + 1, 256, seed=45)
     res = rnd(M, N, seed=46)
     amap = rowmap(d1=10)                        # row m -> add row m // 10
-    out = torch.empty(M, N, device=dev, dtype=dt)
+    out = nan_out(M, N, device=dev, dtype=dt)
     ops.rows_gemm(x.to(dev, dt), w.to(dev, dt), out, ln=(g.to(dev), b.to(dev)), bias=bias.to(dev),
                   add=add.to(dev, dt), addmap=amap, add_ncols=256, act=L.ACT_GELU, res=res.to(dev, dt))
     xn = F.layer_norm(x.to(dt).double(), (D,), g.double(), b.double(), 1e-5)
@@ -869,7 +883,7 @@ def test_rows_gemm_ln_add_res_and_convt(dt, M, rows_variant):
     wt = rnd(D, co, 2, 2, seed=48) / 8
     bt = rnd(co, seed=49)
     Wg = wt.permute(2, 3, 1, 0).reshape(4 * co, D).contiguous()
-    o2 = torch.empty(S * 4 * H * W_, co, device=dev, dtype=dt)
+    o2 = nan_out(S * 4 * H * W_, co, device=dev, dtype=dt)
     ops.rows_gemm(xs.to(dev, dt), Wg.to(dev, dt), o2, bias=bt.repeat(4).to(dev), store=(2, H, W_, co))
     ref2 = F.conv_transpose2d(xs.to(dt).double().reshape(S, H, W_, D).permute(0, 3, 1, 2), wt.to(dt).double(),
                               bt.double(), stride=2)
@@ -887,7 +901,7 @@ def test_rows_mlp(dt, act, rows_variant):
     w2, b2 = rnd(D, Hd, seed=55) / math.sqrt(Hd), rnd(D, seed=56)
     x = rnd(M, D, seed=57)
     yd, xd = y.to(dev, dt), x.to(dev, dt)
-    out = torch.empty_like(xd)
+    out = nan_like(xd)
     ops.rows_mlp(yd, w1.to(dev, dt), b1.to(dev), w2.to(dev, dt), out, ln=(g.to(dev), b.to(dev)), b2=b2.to(dev),
                  act=act, res=yd, res2=xd)
     yn = F.layer_norm(y.to(dt).double(), (D,), g.double(), b.double(), 1e-5).to(dt).double()
@@ -928,18 +942,18 @@ def test_conv3x3_decoder_shapes(W_, c1, c2, co, gn, lds):
     ref = F.conv2d(xin.permute(0, 3, 1, 2), w.to(dt).double(), padding=1)
     L.tune("conv_mode", lds)
     try:
-        out = torch.empty(S * H * W_, co, device=dev, dtype=dt)
+        out = nan_out(S * H * W_, co, device=dev, dtype=dt)
         xs = x1.reshape(-1, c1).contiguous().to(dev, dt)
         wk = w.permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev, dt)
         kw = dict(S=S, H=H, W=W_, c1=c1, src2=x2.reshape(-1, c2).contiguous().to(dev, dt) if c2 else None, c2=c2,
                   src2_div=T, gn=(mean.to(dev), rstd.to(dev), gam.to(dev), bet.to(dev), 16) if gn else None)
         tile = ops.conv3x3_stats_tile(xs, wk, **kw)
         tiles = H * W_ // tile
-        st = torch.empty(S * tiles * (co // 16) * 2, device=dev)
+        st = nan_out(S * tiles * (co // 16) * 2, device=dev)
         ops.conv3x3(xs, wk, out, stats=st, **kw)
         close(out.reshape(S, H, W_, co).permute(0, 3, 1, 2), ref, atol=3e-2, rtol=1e-2, what="conv decoder")
-        m_ = torch.empty(S * (co // 16), device=dev)
-        r_ = torch.empty_like(m_)
+        m_ = nan_out(S * (co // 16), device=dev)
+        r_ = nan_like(m_)
         ops.groupnorm_stats(st, S, tiles, co // 16, tile * 16, m_, r_)
         gref = ref.reshape(S, co // 16, 16, H * W_)
         close(m_, gref.mean((-1, -2)).reshape(-1), atol=2e-3, what="gn mean")
@@ -954,7 +968,7 @@ def test_convt64_gn():
     gam, bet = rnd(C, seed=63) + 1, rnd(C, seed=64)
     wt, bt = rnd(C, co, 2, 2, seed=65) / 8, rnd(co, seed=66)
     xd = x.reshape(-1, C).to(dev, torch.bfloat16)
-    out = torch.empty(S * 4 * H * W_, co, device=dev, dtype=torch.bfloat16)
+    out = nan_out(S * 4 * H * W_, co, device=dev, dtype=torch.bfloat16)
     Wg = wt.permute(2, 3, 1, 0).reshape(4 * co, C).contiguous()
     ops.convt64_gn(xd, Wg.to(dev, torch.bfloat16), out, HW=H * W_,
                    gn=(mean.to(dev), rstd.to(dev), gam.to(dev), bet.to(dev), 16), bias=bt.repeat(4).to(dev),
@@ -972,11 +986,11 @@ def test_text_helpers():
     n, ctx, Wd, vocab = 3, 16, 64, 50
     tok = torch.randint(0, vocab, (n, ctx), generator=torch.Generator().manual_seed(3)).int()
     emb, pos = rnd(vocab, Wd, seed=36), rnd(ctx, Wd, seed=37)
-    x = torch.empty(n * ctx, Wd, device=dev)
+    x = nan_out(n * ctx, Wd, device=dev)
     ops.token_embed(tok.to(dev), emb.to(dev), pos.to(dev), x)
     ref = emb[tok.long()] + pos
     close(x, ref.reshape(-1, Wd), atol=1e-6, what="token_embed")
-    e = torch.empty(n, Wd, device=dev)
+    e = nan_out(n, Wd, device=dev)
     ops.eot_gather(x, tok.to(dev), e)
     close(e, ref[torch.arange(n), tok.long().argmax(-1)], atol=1e-6, what="eot")
 
@@ -990,7 +1004,7 @@ def test_avgpool_and_upsample_add_rows(dt, pool):
     S, H, W, C = 5, 24, 24, 128
     ph, pw = pool
     x = rnd(S, H, W, C, seed=31).to(dt)
-    xp = torch.empty(S * (H // ph) * (W // pw), C, device=dev, dtype=dt)
+    xp = nan_out(S * (H // ph) * (W // pw), C, device=dev, dtype=dt)
     ops.avgpool_rows(x.to(dev).reshape(-1, C), xp, S=S, H=H, W=W, C=C, pool=pool)
     ref_p = F.avg_pool2d(x.float().permute(0, 3, 1, 2), pool)                    # (S, C, Hp, Wp)
     close(xp.reshape(S, H // ph, W // pw, C).permute(0, 3, 1, 2), ref_p,
@@ -1016,7 +1030,7 @@ def test_sliding_crops_and_merge_vs_oracle_ops():
     for i, im in enumerate(imgs):
         raw[i, :, :im.shape[1], :im.shape[2]] = im
     sizes = torch.tensor(shapes, dtype=torch.int32)
-    crops = torch.empty(2 * 5, 3, k, k, device=dev)
+    crops = nan_out(2 * 5, 3, k, k, device=dev)
     ops.sliding_crops(raw.to(dev), sizes.to(dev), crops, out_res=res, kernel=k, stride=stride)
     for i, im in enumerate(imgs):
         x = F.interpolate(im.unsqueeze(0), size=[res, res], mode="bilinear", align_corners=False).squeeze()
@@ -1026,7 +1040,7 @@ def test_sliding_crops_and_merge_vs_oracle_ops():
         close(crops[5 * i:5 * i + 5], ref, atol=2e-3, what=f"crops {i}")
     T = 7
     lg = rnd(2 * 5, T, 96, 96, seed=44, scale=4.0)
-    merged = torch.empty(2, T, res, res, device=dev)
+    merged = nan_out(2, T, res, res, device=dev)
     ops.sliding_merge(lg.to(dev), merged, kernel=k, stride=stride, out_res=res)
     for i in range(2):
         o = F.interpolate(lg[5 * i:5 * i + 5], size=k, mode="bilinear", align_corners=False).sigmoid()
@@ -1039,7 +1053,7 @@ def test_sliding_crops_and_merge_vs_oracle_ops():
     lib = L.load()
     mv = {}
     for v in (1, 2):
-        mv[v] = torch.empty_like(merged)
+        mv[v] = nan_like(merged)
         try:
             L.tune("merge_variant", v)
             ops.sliding_merge(lg.to(dev), mv[v], kernel=k, stride=stride, out_res=res)
@@ -1054,7 +1068,7 @@ def test_sliding_crops_and_merge_vs_oracle_ops():
     lg2 = rnd(1 * 5, 3, 90, 90, seed=45, scale=4.0)
     m2 = {}
     for v in (0, 2):
-        m2[v] = torch.empty(1, 3, r2, r2, device=dev)
+        m2[v] = nan_out(1, 3, r2, r2, device=dev)
         try:
             L.tune("merge_variant", v)
             ops.sliding_merge(lg2.to(dev), m2[v], kernel=k2, stride=s2, out_res=r2)
@@ -1062,7 +1076,7 @@ def test_sliding_crops_and_merge_vs_oracle_ops():
         finally:
             L.tune("merge_variant", 0)
     assert (m2[0] - m2[2]).abs().max().item() <= 1e-6
-    out = torch.empty(1, T, 480, 400, device=dev)
+    out = nan_out(1, T, 480, 400, device=dev)
     ops.resize_bilinear(merged[:1], out, crop=(res, res))
     ref = F.interpolate(merged[:1].cpu(), size=(480, 400), mode="bilinear", align_corners=False)
     close(out, ref, atol=1e-6, what="resize")
@@ -1086,12 +1100,12 @@ def test_swin_window_attention_fused_vs_unfused(shift, variant):
     bias = rnd(3 * D, seed=55, scale=0.1).to(dev)
     gqk = rnd(B * HW, 2 * D, seed=56, scale=0.5).to(dev, dt)
     gmap = rowmap(d1=T * HW, s1=HW, d2=1, m2=HW, s2=1)
-    qkv = torch.empty(R, 3 * D, device=dev, dtype=dt)
+    qkv = nan_out(R, 3 * D, device=dev, dtype=dt)
     ops.rows_gemm(X, W, qkv, ln=(g1, b1), bias=bias, add=gqk, addmap=gmap, add_ncols=2 * D)
-    ref = torch.empty(R, D, device=dev, dtype=dt)
+    ref = nan_out(R, D, device=dev, dtype=dt)
     ops.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ref, n_seq=S * 4, seq_len=144, n_heads=4,
                   head_dim=32, scale=32 ** -0.5, mode=1, img_hw=(24, 24), window=12, shift=shift)
-    out = torch.empty(R, D, device=dev, dtype=dt)
+    out = nan_out(R, D, device=dev, dtype=dt)
     try:
         L.tune("swin_variant", variant)
         ops.swin_window_attention(X, (g1, b1), W, bias, gqk, gmap, out, S=S, img_hw=(24, 24), window=12, shift=shift,
@@ -1223,12 +1237,12 @@ def test_upconv3x3_folded_convtranspose(ci, m, cg, co, H, gn_src):
     ref = F.conv2d(xin, wc.double(), padding=1)                              # (S, co, 2H, 2H)
     comp, tap_b = CatSegEngine._upconv_weights(wt, bt, wc[:, :m])
     wg = wc[:, m:].to(dt).float().permute(0, 2, 3, 1).reshape(co, -1).contiguous().to(dev)
-    part = torch.empty(B * H * H, 4 * co, device=dev)
+    part = nan_out(B * H * H, 4 * co, device=dev)
     ops.upconv_addend(g.permute(0, 2, 3, 1).contiguous().to(dev, dt), wg, tap_b.to(dev), part, B=B, H2=2 * H, W2=2 * H)
-    out = torch.empty(S * 4 * H * H, co, device=dev, dtype=dt)
+    out = nan_out(S * 4 * H * H, co, device=dev, dtype=dt)
     tile = ops.upconv3x3_stats_tile()
     ntl = 4 * H * H // tile
-    st = torch.empty(S * ntl * (co // 16) * 2, device=dev)
+    st = nan_out(S * ntl * (co // 16) * 2, device=dev)
     gn = None
     if gn_src:
         gn = (mean.to(dev), rstd.to(dev), gam.to(dev), bet.to(dev), 16)
@@ -1241,7 +1255,7 @@ def test_upconv3x3_folded_convtranspose(ci, m, cg, co, H, gn_src):
     assert err.mean().item() <= 2e-3, err.mean().item()
     # the one-barrier-per-chunk ring (tuning knob ring_onebar 1, default) equals the two-barrier form bit for bit
     L.load()
-    out1, st1 = torch.empty_like(out), torch.empty_like(st)
+    out1, st1 = nan_like(out), nan_like(st)
     try:
         L.tune("ring_onebar", 0)
         ops.upconv3x3(z.permute(0, 2, 3, 1).contiguous().to(dev, dt), comp.to(dev, dt), out1, S=S, H=H, W=H, c1=ci,
@@ -1250,8 +1264,8 @@ def test_upconv3x3_folded_convtranspose(ci, m, cg, co, H, gn_src):
     finally:
         L.tune("ring_onebar", 1)
     assert torch.equal(out1, out) and torch.equal(st1, st)
-    mean1 = torch.empty(S * (co // 16), device=dev)
-    rstd1 = torch.empty_like(mean1)
+    mean1 = nan_out(S * (co // 16), device=dev)
+    rstd1 = nan_like(mean1)
     ops.groupnorm_stats(st, S, ntl, co // 16, tile * 16, mean1, rstd1)
     gref = got.reshape(S, co // 16, -1)
     close(mean1, gref.mean(-1).reshape(-1), atol=1e-4, what="gn mean")
@@ -1348,7 +1362,7 @@ def test_mlp_barrier_lean_bit_identical(act, M):
     try:
         for v in (0, 1):
             L.tune("mlp_variant", v)
-            o1 = torch.empty_like(y)
+            o1 = nan_like(y)
             ops.rows_mlp(y, w1, b1, w2, o1, ln=(g, b), b2=b2, act=act, res=y,
                          res2=x if act == L.ACT_RELU else None)
             o2 = x.clone()
@@ -1384,7 +1398,7 @@ def test_mlp_gelu_forms_vs_fp64(M):
     try:
         for f in (0, 1):
             L.tune("gelu_form", f)
-            o1 = torch.empty_like(y)
+            o1 = nan_like(y)
             ops.rows_mlp(y, w1, b1, w2, o1, ln=(g, b), b2=b2, act=L.ACT_GELU, res=y)
             o2 = x.clone()
             ops.swin_proj_mlp(y, o2, wp, bp, w1, b1, w2, b2, o2, ln=(g, b))

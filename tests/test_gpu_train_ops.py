@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import poison  # noqa: E402
 from cat_seg import _lib as L  # noqa: E402
 from cat_seg import ops, train_ops as TO  # noqa: E402
 from oracle import catseg_oracle as O  # noqa: E402
@@ -24,7 +25,18 @@ def rel(a, b):
     return ((a - b).abs().max() / (b.abs().max() + 1e-30)).item()
 
 
+def nan_out(*shape, device=DEV):
+    """An fp32 output its call is documented to overwrite completely (beta = 0), prefilled with NaN: an
+    element the kernel leaves unwritten cannot pass on what an earlier test left in the allocator's block."""
+    return poison.filled(tuple(shape), torch.float32, device)
+
+
+def nan_like(t):
+    return poison.filled(tuple(t.shape), t.dtype, t.device)
+
+
 def close(a, b, tol=1e-4):
+    assert not torch.isnan(a).any(), f"{int(torch.isnan(a).sum())} NaN element(s) in the result"
     e = rel(a, b)
     assert e <= tol, f"rel err {e:.3e} > {tol}"
 
@@ -73,7 +85,7 @@ def test_gemm_ex_split_bf16_forms(terms, tol, M, N, K):
                     continue
                 a_sm, a_sk = (1, M) if a_t else (K, 1)
                 b_sk, b_sn = (1, K) if b_t else (N, 1)
-                out = torch.empty(M, N, device=DEV)
+                out = nan_out(M, N, device=DEV)
                 TO.gemm_ex(dev(A.t() if a_t else A), a_sm, a_sk, dev(B.t() if b_t else B), b_sk, b_sn, out,
                            M=M, N=N, K=K)
                 close(out, ref, tol)
@@ -152,13 +164,13 @@ def test_groupnorm_relu_stats_and_backward(S, H, W, C, cpg):
     xr, gr, br = (t.clone().requires_grad_(True) for t in (x, gm, bt))
     F.relu(F.group_norm(xr, C // cpg, gr, br, 1e-5)).backward(dy)
     xn = dev(x.permute(0, 2, 3, 1))
-    mean = torch.empty(S * C // cpg, device=DEV)
-    rstd = torch.empty_like(mean)
+    mean = nan_out(S * C // cpg, device=DEV)
+    rstd = nan_like(mean)
     TO.groupnorm_stats_rows(xn, S, H * W, C, cpg, mean, rstd)
     xs = x.reshape(S, C // cpg, -1)
     close(mean, xs.mean(-1).reshape(-1), 1e-5)
     close(rstd, (1 / torch.sqrt(xs.var(-1, unbiased=False) + 1e-5)).reshape(-1), 1e-5)
-    dx = torch.empty_like(xn)
+    dx = nan_like(xn)
     dg = torch.zeros(C, device=DEV)
     db = torch.zeros(C, device=DEV)
     TO.groupnorm_relu_backward(xn, dev(dy.permute(0, 2, 3, 1)), dx, S=S, HW=H * W, C_=C, cpg=cpg, mean=mean, rstd=rstd,
@@ -175,7 +187,7 @@ def test_sum_classes_and_pixels():
     out = torch.ones(B * HW, C, device=DEV)
     TO.sum_classes(dev(x), out, B=B, T=T, HW=HW, C_=C, beta=1)
     close(out, xr.sum(1).reshape(B * HW, C) + 1, 1e-6)
-    out2 = torch.empty(T, C, device=DEV)
+    out2 = nan_out(T, C, device=DEV)
     TO.sum_pixels(dev(x), out2, B=B, T=T, HW=HW, C_=C)
     close(out2, xr.sum((0, 2)), 1e-6)
 
@@ -190,7 +202,7 @@ def test_avgpool_and_upsample_ac_backward():
     y.backward(dy)
     # upsample backward to the pooled grid, then the pool backward
     dyn = dev(dy.permute(0, 2, 3, 1))
-    dxp = torch.empty(S * 12 * 12, C, device=DEV)
+    dxp = nan_out(S * 12 * 12, C, device=DEV)
     TO.upsample_ac_backward_rows(dyn, dxp, S=S, H=H, W=W, C_=C, Hp=12, Wp=12)
     dx = torch.ones(S * H * W, C, device=DEV)
     TO.avgpool_backward_rows(dxp, dx, S=S, H=H, W=W, C_=C, pool=(2, 2), beta=1)
@@ -217,7 +229,7 @@ def test_convtranspose_backward_via_gather(k):
     y = F.conv_transpose2d(xr, wr, br, stride=k)
     dy = g(*y.shape, seed=22)
     y.backward(dy)
-    G = torch.empty(S * h * h, k * k * cout, device=DEV)
+    G = nan_out(S * h * h, k * k * cout, device=DEV)
     TO.convt_gather(dev(dy.permute(0, 2, 3, 1)).reshape(-1, cout), G, S=S, hin=h, win=h, k=k, cout=cout)
     Wg = dev(w.permute(2, 3, 1, 0).reshape(k * k * cout, cin))      # [(ky, kx, co)][ci]
     X = dev(x.permute(0, 2, 3, 1).reshape(-1, cin))
@@ -225,7 +237,7 @@ def test_convtranspose_backward_via_gather(k):
     close(dX, xr.grad.permute(0, 2, 3, 1).reshape(-1, cin))
     dWg = TO.mm(G.t(), X)
     close(dWg.reshape(k, k, cout, cin).permute(3, 2, 0, 1), wr.grad)
-    db = torch.empty(cout, device=DEV)
+    db = nan_out(cout, device=DEV)
     TO.colsum(G, db, rows=S * h * h * k * k, cols=cout, ld=cout)
     close(db, br.grad)
 
@@ -268,11 +280,11 @@ def test_window_attention_backward(shift):
     o.backward(dout)
     # the forward kernel's own output feeds D_q = dO . O
     qkvd = dev(qkv)
-    od = torch.empty(R, D, device=DEV)
+    od = nan_out(R, D, device=DEV)
     ops.attention(qkvd[:, :D], qkvd[:, D:2 * D], qkvd[:, 2 * D:], od, n_seq=S * 4, seq_len=ws * ws, n_heads=nh,
                   head_dim=D // nh, scale=(D // nh) ** -0.5, mode=1, img_hw=(H, W), window=ws, shift=shift)
     close(od, o, 1e-5)
-    dqkv = torch.empty(R, 3 * D, device=DEV)
+    dqkv = nan_out(R, 3 * D, device=DEV)
     TO.window_attention_backward(qkvd, od, dev(dout), dqkv, S=S, img_hw=(H, W), window=ws, shift=shift, n_heads=nh,
                                  head_dim=D // nh, scale=(D // nh) ** -0.5)
     close(dqkv[:, :D], qr.grad)
@@ -300,11 +312,11 @@ def test_dense_attention_backward(n_seq, L_, nh, causal):
     o = (s.softmax(-1) @ heads(vr)).permute(0, 2, 1, 3).reshape(R, W)
     o.backward(dout)
     qkvd = dev(qkv)
-    od = torch.empty(R, W, device=DEV)
+    od = nan_out(R, W, device=DEV)
     ops.attention(qkvd[:, :W], qkvd[:, W:2 * W], qkvd[:, 2 * W:], od, n_seq=n_seq, seq_len=L_, n_heads=nh,
                   head_dim=hd, scale=hd ** -0.5, causal=causal)
     close(od, o, 1e-5)
-    dqkv = torch.empty(R, 3 * W, device=DEV)
+    dqkv = nan_out(R, 3 * W, device=DEV)
     TO.attention_backward(qkvd, od, dev(dout), dqkv, n_seq=n_seq, seq_len=L_, n_heads=nh, head_dim=hd,
                           scale=hd ** -0.5, causal=causal)
     close(dqkv[:, :W], qr.grad)
@@ -332,9 +344,9 @@ def test_linear_attention_backward(T, n_pad):
     out = O.linear_attention(seq(qr, kp), seq(kr, kp), seq(vr, vp))[:, :T]
     out = out.reshape(B, HW, T, D).permute(0, 2, 1, 3).reshape(R, D)
     out.backward(dy)
-    dqkv = torch.empty(R, 3 * D, device=DEV)
-    dkp = torch.empty(D, device=DEV)
-    dvp = torch.empty(D, device=DEV)
+    dqkv = nan_out(R, 3 * D, device=DEV)
+    dkp = nan_out(D, device=DEV)
+    dvp = nan_out(D, device=DEV)
     kw = dict(k_pad=dev(kv_pad[0]), v_pad=dev(kv_pad[1]), dk_pad=dkp, dv_pad=dvp) if n_pad else {}
     TO.linear_attention_backward(dev(qkv), dev(dy), dqkv, B=B, T=T, HW=HW, n_heads=nh, head_dim=hd, n_pad=n_pad, **kw)
     close(dqkv[:, :D], qr.grad)
@@ -363,19 +375,19 @@ def test_conv2d_forward_dgrad_wgrad(cin, cout, k, relu, S):
     y.backward(dy)
     xn = dev(x.permute(0, 2, 3, 1).reshape(-1, cin))
     wt = dev(w.permute(2, 3, 1, 0).reshape(k * k * cin, cout))         # [(tap, ci)][co]
-    yd = torch.empty(S * H * W, cout, device=DEV)
+    yd = nan_out(S * H * W, cout, device=DEV)
     TO.conv2d(xn, wt, yd, S=S, H=H, W=W, cin=cin, cout=cout, ksize=k, bias=dev(b), act=L.ACT_RELU if relu else 0)
     close(yd, y.permute(0, 2, 3, 1).reshape(-1, cout), 1e-5)
     dyn = dev(dy.permute(0, 2, 3, 1).reshape(-1, cout))
     if relu:
         dyn = TO.act_backward(yd, dyn, L.ACT_RELU)
-    dw = torch.empty(k * k * cin, cout, device=DEV)
+    dw = nan_out(k * k * cin, cout, device=DEV)
     TO.conv2d_wgrad(xn, dyn, dw, S=S, H=H, W=W, cin=cin, cout=cout, ksize=k)
     close(dw.reshape(k, k, cin, cout).permute(3, 2, 0, 1), wr.grad)
     if cin % 4 == 0:
         # data gradient: conv of dY with the flipped, transposed weight [(tap, co)][ci]
         wf = dev(w.flip(2, 3).permute(2, 3, 0, 1).reshape(k * k * cout, cin))
-        dx = torch.empty(S * H * W, cin, device=DEV)
+        dx = nan_out(S * H * W, cin, device=DEV)
         TO.conv2d(dyn, wf, dx, S=S, H=H, W=W, cin=cout, cout=cin, ksize=k)
         close(dx, xr.grad.permute(0, 2, 3, 1).reshape(-1, cin))
 
@@ -426,8 +438,8 @@ def test_head_conv_backward():
     y = F.conv2d(xr, wr, padding=1)
     dl = g(*y.shape, seed=34)
     y.backward(dl)
-    dx = torch.empty(S * H * W, C, device=DEV)
-    dw = torch.empty(9, C, device=DEV)
+    dx = nan_out(S * H * W, C, device=DEV)
+    dw = nan_out(9, C, device=DEV)
     TO.head_conv_backward(dev(x.permute(0, 2, 3, 1)), dev(dl), dev(w[0].permute(1, 2, 0).reshape(9, C)), dx, dw,
                           S=S, H=H, W=W, C_=C)
     close(dx, xr.grad.permute(0, 2, 3, 1).reshape(-1, C))
