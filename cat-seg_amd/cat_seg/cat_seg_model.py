@@ -11,6 +11,8 @@ same config keys, with `forward(batched_inputs: list[dict]) -> list[dict]`:
 The reference returns results for batched_inputs[0] only (cat_seg_model.py:227-229);
 this boundary returns one result per input image by default
 (MODEL.CATSEG_HIP.RETURN_ALL_IMAGES; set False for the reference's exact behaviour).
+With MODEL.CATSEG_HIP.TILED.ENABLED an image of any size is segmented at its own resolution: cut into
+tiles, each through the network as an image of its own, merged on the device (engine.forward_tiled).
 
 Everything between the input copy and the returned tensors runs in the HIP kernels of
 libcatseg_hip.so through `CatSegEngine`; there is no CPU or PyTorch-op fallback.
@@ -27,7 +29,7 @@ import torch
 from torch import nn
 from torch.nn.modules.module import _IncompatibleKeys
 
-from . import custom_ops, ops
+from . import custom_ops, ops, tiling
 from .arch import CatSegArch, arch_from_cfg
 from .engine import CatSegEngine
 from .modeling.heads.cat_seg_head import CATSegHead  # noqa: F401  (registers the head)
@@ -68,10 +70,24 @@ class CATSeg(nn.Module):
                  train_class_json: str, test_class_json: str, sliding_window: bool, clip_finetune: str,
                  backbone_multiplier: float, clip_pretrained: str, arch: Optional[CatSegArch] = None,
                  dtype: str = "bf16", return_all_images: bool = True, synthetic_seed: int = 0,
-                 vit_fp8: bool = False, graph: bool = True, output: str = "probs"):
+                 vit_fp8: bool = False, graph: bool = True, output: str = "probs", tiled: bool = False,
+                 tiled_tile: int = 384, tiled_stride: int = 256, tiled_batch: int = 8, tta_merge: str = "host"):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
+        # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
+        self.tiled = bool(tiled)
+        self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
+        if self.tiled:
+            if sliding_window:
+                raise ValueError("CATSeg: MODEL.CATSEG_HIP.TILED and TEST.SLIDING_WINDOW are two ways to cut one image "
+                                 "into windows: enable one of them")
+            if tta_merge == "device":
+                raise ValueError("CATSeg: MODEL.CATSEG_HIP.TILED has no single logits tensor per image, which "
+                                 "MODEL.CATSEG_HIP.TTA_MERGE 'device' merges: use TTA_MERGE 'host'")
+            tiling.check_tile_stride(self.tiled_tile, self.tiled_stride, max(int(size_divisibility), 1))
+            if not 1 <= self.tiled_batch <= 32:
+                raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.TILED.BATCH must be in [1, 32], got {tiled_batch}")
         self.output = output
         self.backbone = backbone
         self.sem_seg_head = sem_seg_head
@@ -114,6 +130,7 @@ class CATSeg(nn.Module):
     @classmethod
     def from_config(cls, cfg):
         hip = cfg.MODEL.get("CATSEG_HIP", {}) if hasattr(cfg.MODEL, "get") else {}
+        tiled = (hip.get("TILED", None) if hip else None) or {}
         return {
             "backbone": None,
             "sem_seg_head": build_sem_seg_head(cfg, None),
@@ -135,6 +152,11 @@ class CATSeg(nn.Module):
             "vit_fp8": bool(hip.get("VIT_FP8", False)) if hip else False,
             "graph": bool(hip.get("GRAPH", True)) if hip else True,
             "output": str(hip.get("OUTPUT", "probs")) if hip else "probs",
+            "tiled": bool(tiled.get("ENABLED", False)),
+            "tiled_tile": int(tiled.get("TILE", 384)),
+            "tiled_stride": int(tiled.get("STRIDE", 256)),
+            "tiled_batch": int(tiled.get("BATCH", 8)),
+            "tta_merge": str(hip.get("TTA_MERGE", "host")) if hip else "host",
         }
 
     # ------------------------------------------------------------------ parameters
@@ -389,6 +411,9 @@ class CATSeg(nn.Module):
         if self.sliding_window:
             raise RuntimeError("CATSeg.forward_logits does not serve TEST.SLIDING_WINDOW: the sliding branch "
                                "merges its windows before the resize and has no single logits tensor")
+        if self.tiled:
+            raise RuntimeError("CATSeg.forward_logits does not serve MODEL.CATSEG_HIP.TILED: the tiled branch "
+                               "merges its tiles before the resize and has no single logits tensor")
         if torch.compiler.is_compiling():
             raise RuntimeError("CATSeg.forward_logits cannot be traced by torch.compile: call it eagerly")
         with torch.no_grad():
@@ -407,6 +432,8 @@ class CATSeg(nn.Module):
             return self._training_loss(batched_inputs)
         if self.sliding_window:
             return self._forward_sliding(batched_inputs)
+        if self.tiled:
+            return self._forward_tiled(batched_inputs)
         if torch.compiler.is_compiling():
             return self._forward_traced(batched_inputs)
         with torch.no_grad():
@@ -431,6 +458,34 @@ class CATSeg(nn.Module):
                 results.append({"sem_seg": out[0]})
             return results
 
+    def _forward_tiled(self, batched_inputs: List[dict]):
+        """MODEL.CATSEG_HIP.TILED eval: every image (or image 0 in the reference mode) at its own resolution
+        through CatSegEngine.forward_tiled; the map is at input resolution, so a dict's height / width must
+        be its image's size."""
+        if torch.compiler.is_compiling():
+            raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.TILED cannot be traced by torch.compile: the "
+                               "tile grid follows each image's size; call it eagerly")
+        with torch.no_grad():
+            eng = self.engine
+            self.sem_seg_head.predictor.get_text_embeds()
+            n = len(batched_inputs) if self.return_all_images else 1
+            results = []
+            for x in batched_inputs[:n]:
+                im = x["image"]
+                ih, iw = int(im.shape[-2]), int(im.shape[-1])
+                if (int(x.get("height", ih)), int(x.get("width", iw))) != (ih, iw):
+                    raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.TILED returns the map at input resolution, but the "
+                                     f"image is {ih} x {iw} and height / width ask for {x.get('height', ih)} x "
+                                     f"{x.get('width', iw)}: set INPUT.MIN_SIZE_TEST 0 (CATSegTestDatasetMapper then "
+                                     f"applies no resize)")
+                img = im.to(eng.device, torch.float32).contiguous()
+                out = eng.forward_tiled(img, self.output == "labels", tile=self.tiled_tile,
+                                        stride=self.tiled_stride, batch=self.tiled_batch)
+                if self.output == "labels":
+                    results.append({"sem_seg_labels": out[0], "sem_seg_score": out[1]})
+                else:
+                    results.append({"sem_seg": out})
+            return results
 
     def _training_loss(self, batched_inputs: List[dict]):
         """The training branch (cat_seg_model.py:136-146,178-203): fp32 CLIP dense features + hooks and

@@ -198,4 +198,13 @@ def add_cat_seg_config(cfg):
     # reference's merge; "probs" models only) | "device" merges the views' logits in one kernel
     # (catseg_postprocess_tta) and also serves "labels" models
     cfg.MODEL.CATSEG_HIP.TTA_MERGE = "host"
+    # tiled inference at native resolution: every image cut into TILE x TILE windows STRIDE apart (the last
+    # one of an axis shifted back to end at the border), each through the network as an image of its own,
+    # the windows' probabilities averaged on the device (catseg_tiled_merge); the map is at input
+    # resolution.  TILE a multiple of SIZE_DIVISIBILITY, TILE / 2 <= STRIDE <= TILE, BATCH tiles per launch
+    cfg.MODEL.CATSEG_HIP.TILED = C()
+    cfg.MODEL.CATSEG_HIP.TILED.ENABLED = False
+    cfg.MODEL.CATSEG_HIP.TILED.TILE = 384
+    cfg.MODEL.CATSEG_HIP.TILED.STRIDE = 256     # the reference's int(384 * (1 - 0.333))
+    cfg.MODEL.CATSEG_HIP.TILED.BATCH = 8
     return cfg

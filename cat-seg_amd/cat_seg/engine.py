@@ -778,8 +778,68 @@ class CatSegEngine:
         ops.postprocess(logits, out, crop=(min(h, ih), min(w, iw)))
         return out
 
+    # ------------------------------------------------------------------ tiled eval at native resolution
+    def forward_tiled(self, image: torch.Tensor, labels: bool = False, *, tile: int = 384, stride: int = 256,
+                      batch: int = 8):
+        """One scene of any size at its own resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling holds the
+        grid): the tiles, row-major in groups of `batch`, through catseg_tile_crops -> head_logits as
+        images of the tile's size, their logits kept for the tile rows the merge still needs (at most 3,
+        moved down as rows retire), and one catseg_tiled_merge per step of tiling.merge_schedule.
+        image fp32 (3, H, W) 0-255 on the device.  Returns probabilities (T, H, W) fp32, or with
+        labels=True (labels (H, W) int32, score (H, W) fp32) without any (T, H, W) volume: beyond the image
+        and the outputs, 3 tile rows of logits and the group in flight are live, whatever H."""
+        from . import tiling
+        if not 1 <= batch <= 32:
+            raise ValueError(f"forward_tiled: TILED.BATCH must be in [1, 32] (catseg_tile_crops), got {batch}")
+        assert image.dtype == _f32 and image.is_contiguous() and image.dim() == 3 and image.shape[0] == 3
+        dev = self.device
+        H, W = int(image.shape[-2]), int(image.shape[-1])
+        g = tiling.tile_grid(H, W, tile, stride)
+        d = max(self.arch.size_divisibility, 1)
+        ch, cw = _round_up(g.th, d), _round_up(g.tw, d)      # the plain path's canvas of an image of (th, tw)
+        nx = g.nx
+        steps = list(tiling.merge_schedule(H, g.th, g.sy))
+        tiles = [(r, c) for r in range(g.ny) for c in range(nx)]
+        sizes = torch.tensor([[g.th, g.tw]] * min(batch, len(tiles)), dtype=torch.int32, device=dev)
+        lab = torch.empty(H, W, device=dev, dtype=torch.int32) if labels else None
+        sc = torch.empty(H, W, device=dev, dtype=_f32) if labels else None
+        probs = ring = crop = None
+        base = si = 0                                            # tile row in slot 0 of the ring; next step
+        for i in range(0, len(tiles), batch):
+            grp = tiles[i:i + batch]
+            canvas = torch.empty(len(grp), 3, ch, cw, device=dev, dtype=_f32)
+            ops.tile_crops(image, [(g.oys[r], g.oxs[c]) for r, c in grp], g.th, g.tw, canvas)
+            lg = self.head_logits(canvas, sizes[:len(grp)])
+            if ring is None:
+                T, h, w = lg.shape[1:]
+                ring = torch.empty(min(3, g.ny) * nx, T, h, w, device=dev, dtype=_f32)
+                crop = (min(h, g.th), min(w, g.tw))
+                if not labels:
+                    probs = torch.empty(T, H, W, device=dev, dtype=_f32)
+            j = 0
+            while j < len(grp):
+                r, c = grp[j]
+                n = min(len(grp) - j, nx - c)                    # this group's tiles of tile row r
+                if c == 0 and steps[si][0] > base:               # a new tile row: retire the rows no step needs
+                    k = steps[si][0] - base
+                    for q in range(k, r - base):
+                        ring[(q - k) * nx:(q - k + 1) * nx].copy_(ring[q * nx:(q + 1) * nx])
+                    base += k
+                ring[(r - base) * nx + c:(r - base) * nx + c + n].copy_(lg[j:j + n])
+                j += n
+                if c + n < nx:
+                    continue
+                while si < len(steps) and steps[si][0] + steps[si][1] - 1 <= r:      # tile row r is complete
+                    row0, rows, y0, y1 = steps[si]
+                    s = (row0 - base) * nx
+                    ops.tiled_merge(ring[s:s + rows * nx], g, (row0, rows), (y0, y1), crop=crop, probs=probs,
+                                    labels=lab, score=sc)
+                    si += 1
+        assert si == len(steps)
+        return (lab, sc) if labels else probs
+
     # ------------------------------------------------------------------ sliding-window eval
-    SLIDE_KERNEL, SLIDE_OVERLAP, SLIDE_OUT = 384, 0.333, 640      # cat_seg_model.py:158-160
+    SLIDE_KERNEL,SLIDE_OVERLAP, SLIDE_OUT = 384, 0.333, 640      # cat_seg_model.py:158-160
 
     def sliding_logits(self, raw: torch.Tensor, sizes: torch.Tensor, return_crops: bool = False):
         """TEST.SLIDING_WINDOW branch up to the merged probabilities (cat_seg_model.py:156-176,204-213),

@@ -586,6 +586,56 @@ def postprocess_tta(logits, views, *, probs=None, labels=None, score=None):
     return probs, labels, score
 
 
+def tile_crops(image, origins, th, tw, canvas):
+    """Gather the tiles of extent (th, tw) at `origins` [(oy, ox), ...] (host ints, at most 32) of one fp32
+    image (3, H, W) into canvas (B, 3, ch, cw) fp32, ch >= th and cw >= tw; the canvas is written whole,
+    zero beyond (th, tw) (catseg_tile_crops)."""
+    origins = [(int(oy), int(ox)) for oy, ox in origins]
+    B = len(origins)
+    assert image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 3 and image.shape[0] == 3
+    assert canvas.dtype == torch.float32 and canvas.is_contiguous() and tuple(canvas.shape[:2]) == (B, 3)
+    H, W = image.shape[-2:]
+    ch, cw = canvas.shape[-2:]
+    table = (C.c_int32 * (2 * B))(*[e for o in origins for e in o])
+    with _rec("tile_crops", 0, 4 * 3 * B * (th * tw + ch * cw)):
+        call("catseg_tile_crops", image.data_ptr(), H, W, C.cast(table, C.c_void_p), B, int(th), int(tw),
+             canvas.data_ptr(), ch, cw, _stream())
+    return canvas
+
+
+def tiled_merge(logits, geometry, window, rows, *, crop=None, probs=None, labels=None, score=None):
+    """Merge of the tiles' logits of one tiled scene (catseg_tiled_merge; cat_seg.tiling holds the grid):
+    per tile the sigmoid + crop + bilinear resize of `postprocess` to the tile's extent, summed over the
+    covering tiles in row-major tile order and scaled by 1 / count, for output rows rows = (y0, y1).
+    logits (n * nx, T, h, w) fp32 holds the tile rows window = (row0, n) of `geometry` (a tiling.TileGrid,
+    or (H, W, th, tw, sy, sx)); crop the region of a tile's logits that is resized (default all of it).
+    probs (T, H, W) fp32 and / or labels (H, W) int32 with score (H, W) fp32 or None are whole-image
+    tensors; rows outside [y0, y1) and outputs not passed are not written.  Returns (probs, labels, score)."""
+    H, W, th, tw, sy, sx = (int(v) for v in tuple(geometry)[:6])
+    row0, nrows = (int(v) for v in window)
+    y0, y1 = (int(v) for v in rows)
+    n, T, h, w = logits.shape
+    ch, cw = crop if crop is not None else (h, w)
+    if probs is None and labels is None:
+        raise ValueError("tiled_merge: pass probs and / or labels")
+    nx = max(W - tw + sx - 1, 0) // sx + 1
+    if n != nrows * nx:
+        raise ValueError(f"tiled_merge: a window of {nrows} tile rows of {nx} tiles needs {nrows * nx} logits, "
+                         f"got {n}")
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    assert probs is None or (probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == T * H * W)
+    assert labels is None or (labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == H * W)
+    assert score is None or (score.dtype == torch.float32 and score.is_contiguous() and score.numel() == H * W)
+    # the window's crops read once (at most); the rows of the outputs written once
+    nbytes = 4 * (T * n * ch * cw + (y1 - y0) * W * ((T if probs is not None else 0)
+                  + ((1 if score is None else 2) if labels is not None else 0)))
+    with _rec("tiled_merge", 0, nbytes):
+        call("catseg_tiled_merge", logits.data_ptr(), T, h, w, int(ch), int(cw), H, W, th, tw, sy, sx, row0, nrows,
+             y0, y1, 0 if probs is None else probs.data_ptr(), 0 if labels is None else labels.data_ptr(),
+             0 if score is None else score.data_ptr(), _stream())
+    return probs, labels, score
+
+
 def avgpool_rows(x, out, *, S, H, W, C, pool):
     """nn.AvgPool2d(pool) over [S][H][W][C] rows -> out [S][H/ph][W/pw][C] (catseg_avgpool_rows)."""
     ph, pw = pool

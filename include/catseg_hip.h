@@ -409,6 +409,36 @@ int catseg_postprocess_argmax(const float* logits, int64_t B, int T, int h, int 
 int catseg_postprocess_tta(const float* logits, int K, int T, int h, int w, const int32_t* views,
                            float* probs, int32_t* labels, float* score, int H, int W, void* stream);
 
+/* Tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; csrc/post_tiled.hip).  The grid, per axis,
+ * for image extent L, tile t and stride s (cat_seg/tiling.py holds the one definition):
+ *   t' = min(t, L);  n = max(L - t' + s - 1, 0) / s + 1;  o_i = min(i s, L - t'), i = 0 .. n-1
+ * (the last tile is shifted back, never padded); tiles are row-major and all of extent (th, tw).
+ *
+ * catseg_tile_crops — gather B <= 32 tiles of one fp32 image [3][H][W] into a canvas [B][3][ch][cw]
+ * (ch, cw >= th, tw), which is written whole: zero beyond (th, tw).  origins is a HOST int32 [B][2] table
+ * (oy, ox) read at call time and passed to the kernel by value. */
+int catseg_tile_crops(const float* image, int H, int W, const int32_t* origins, int B,
+                      int th, int tw, float* canvas, int ch, int cw, void* stream);
+
+/* catseg_tiled_merge — the merge of the tiles' logits for output rows [y0, y1) of the image, from a WINDOW
+ * of tile rows: logits fp32 [rows * nx][T][h][w] holds tile rows row0 .. row0+rows-1 of the grid that
+ * (H, W, th, tw, sy, sx) defines (th <= H, tw <= W: the t' of the formula; tile / 2 <= stride <= tile).
+ *   p_i(t, y - oy_i, x - ox_i) = the value catseg_postprocess computes on its banded path for tile i:
+ *                                (h, w, crop_h, crop_w) -> (th, tw), sigmoid on the source logit
+ *   s = fp32 sum of p_i over the tiles that cover (y, x), in row-major tile order (sequential adds)
+ *   m = s * (1.0f / (float)count);  probs[t][y][x] = m;  labels[y][x] = first maximum of m over t;
+ *   score[y][x] = that maximum
+ * Ties and NaN as catseg_postprocess_argmax (NaN ranks highest, the first NaN wins).  No atomics: the
+ * result is deterministic, and labels / score equal the argmax / max of probs bit for bit.
+ * Every tile row that covers a row of [y0, y1) must lie in the window (error otherwise).  probs [T][H][W] /
+ * labels [H][W] / score [H][W] are whole-image base pointers; rows outside [y0, y1) are not touched.  probs
+ * or labels may be NULL (not both); score only with labels.  No allocation, copy or synchronise inside.
+ * The source patch of one 16 x 64 output tile inside one tile must fit the 4096-float LDS stage, as for
+ * catseg_postprocess_argmax. */
+int catseg_tiled_merge(const float* logits, int T, int h, int w, int crop_h, int crop_w,
+                       int H, int W, int th, int tw, int sy, int sx, int row0, int rows,
+                       int y0, int y1, float* probs, int32_t* labels, float* score, void* stream);
+
 /* ---------------------------------------------------------------------------
  * catseg_swin_window_attention — fused LayerNorm(norm1) + [q|k|v] projection (+ the
  * per-image guidance half of q and k) + shifted-window multi-head attention, one
