@@ -220,6 +220,9 @@ _SIGS = {
     "catseg_layernorm_fp8": [vp, i64, RowMap, i32, vp, i64, vp, vp, vp, i64, i64, f32, vp],
     "catseg_semseg_confusion": [vp, i64, i64, i64, vp, i32, i32, i32, vp, vp, vp],
     "catseg_semseg_confusion_labels": [vp, i64, i64, vp, i32, i32, i32, vp, vp, vp],
+    "catseg_label_runs_workspace": [i64, i64],
+    "catseg_label_runs_count": [vp, i64, i64, i64, i32, vp, i64, vp],
+    "catseg_label_runs_write": [vp, i64, i64, i64, i32, vp, i64, vp, vp, i64, vp],
     "catseg_rows_gemm": [vp, i64, i64, vp, vp, f32, vp, i64, C.POINTER(RowsEpi), i32, vp],
     "catseg_rows_mlp": [vp, i64, i64, vp, vp, f32, vp, vp, i64, i32, vp, C.POINTER(RowsEpi), i32, vp],
     "catseg_layernorm": [vp, i64, RowMap, i32, vp, i64, i32, vp, vp, i64, i64, f32, vp],

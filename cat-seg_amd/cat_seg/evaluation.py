@@ -17,7 +17,11 @@ from the small (N+1)^2 matrix.  With an `output_dir`, `process()` also keeps the
 RLE records of every prediction (`encode_json_sem_seg`, plain_train_net.py:125,207-228; the RLE
 is pycocotools' `mask.encode`, restated in `coco_rle_encode` since pycocotools is absent) and
 `evaluate()` gathers them over ranks and writes `sem_seg_predictions.json`
-(plain_train_net.py:139-152).
+(plain_train_net.py:139-152).  With `rle="device"` (the default) the records come from the
+column-major label runs of the argmax map, made on the device (`ops.label_runs`,
+catseg_label_runs_*): only the runs cross to the host, where `rle_records_from_runs` reads every
+label's RLE off them; `rle="host"` copies the map and encodes one mask per label as the reference
+does.  Both give the same records and the same file.
 """
 from __future__ import annotations
 
@@ -62,16 +66,25 @@ def coco_rle_encode(mask: np.ndarray) -> dict:
     (tests/test_eval_cpu.py), not against pycocotools itself."""
     mask = np.asarray(mask)
     h, w = mask.shape
+    return {"size": [int(h), int(w)], "counts": rle_counts_to_string(rle_mask_counts(mask))}
+
+
+def rle_mask_counts(mask: np.ndarray) -> list:
+    """maskApi.c rleEncode of one H x W binary mask: the run lengths over its column-major pixels,
+    alternating and starting with a run of zeros (0 when pixel (0, 0) is set)."""
     flat = np.asarray(mask, dtype=bool).ravel(order="F")
     if flat.size == 0:
-        cnts = [0]
-    else:
-        edges = np.flatnonzero(flat[1:] != flat[:-1]) + 1
-        runs = np.diff(np.concatenate(([0], edges, [flat.size])))
-        cnts = ([0] if flat[0] else []) + runs.tolist()
-    # rleToString, vectorised: x_i = c_i - c_{i-2} (i > 2), n_i = the fewest 5-bit groups whose
+        return [0]
+    edges = np.flatnonzero(flat[1:] != flat[:-1]) + 1
+    runs = np.diff(np.concatenate(([0], edges, [flat.size])))
+    return ([0] if flat[0] else []) + runs.tolist()
+
+
+def rle_counts_to_string(counts) -> str:
+    """maskApi.c rleToString of a list of run lengths (the compression described in coco_rle_encode)."""
+    # vectorised: x_i = c_i - c_{i-2} (i > 2), n_i = the fewest 5-bit groups whose
     # two's complement holds x_i (the loop "until the rest is the last group's sign extension")
-    c = np.asarray(cnts, dtype=np.int64)
+    c = np.asarray(counts, dtype=np.int64)
     x = c.copy()
     if c.size > 3:
         x[3:] -= c[1:-2]
@@ -83,8 +96,40 @@ def coco_rle_encode(mask: np.ndarray) -> dict:
     groups = (x[:, None] >> (5 * ks)[None, :]) & 0x1F
     more = ks[None, :] < (n[:, None] - 1)
     chars = groups + 48 + np.where(more, 0x20, 0)
-    out = chars[ks[None, :] < n[:, None]].astype(np.uint8).tobytes().decode("ascii")
-    return {"size": [int(h), int(w)], "counts": out}
+    return chars[ks[None, :] < n[:, None]].astype(np.uint8).tobytes().decode("ascii")
+
+
+def rle_records_from_runs(run_start, run_label, H: int, W: int) -> list:
+    """Every per-label COCO RLE of one H x W label map from its column-major label runs (ops.label_runs:
+    run_start ascending positions p = x * H + y, run_label the label of each run, runs maximal): a list of
+    (label, {"size": [H, W], "counts": str}) in ascending label order, each equal to
+    coco_rle_encode(map == label).  Run i is the interval [start_i, start_{i+1}) (the last ends at H * W); a
+    label's counts are the gaps and lengths of its intervals in order, s_0, e_0 - s_0, s_1 - e_0, ... (a
+    leading 0 by itself when s_0 == 0), plus the rest H * W - e_last when that is positive."""
+    n = int(H) * int(W)
+    start = np.asarray(run_start, dtype=np.int64).ravel()
+    label = np.asarray(run_label).ravel()
+    if start.size != label.size or start.size == 0 or start[0] != 0:
+        raise ValueError("rle_records_from_runs: need one label per run and a first run at position 0")
+    end = np.concatenate((start[1:], [n]))
+    order = np.argsort(label, kind="stable")
+    lab = label[order]
+    # interleaved interval borders s_0, e_0, s_1, e_1, ... of all labels, label by label
+    pts = np.empty(2 * order.size, dtype=np.int64)
+    pts[0::2] = start[order]
+    pts[1::2] = end[order]
+    first = np.concatenate(([0], np.flatnonzero(lab[1:] != lab[:-1]) + 1, [lab.size]))
+    size = [int(H), int(W)]
+    records = []
+    for a, b in zip(first[:-1].tolist(), first[1:].tolist()):
+        p = pts[2 * a:2 * b]
+        counts = np.empty(p.size + 1, dtype=np.int64)
+        counts[0] = p[0]
+        counts[1:-1] = p[1:] - p[:-1]
+        counts[-1] = n - p[-1]
+        records.append((int(lab[a]), {"size": size[:], "counts": rle_counts_to_string(
+            counts if counts[-1] > 0 else counts[:-1])}))
+    return records
 
 
 _OBJ_GROUP = []
@@ -152,7 +197,10 @@ class SemSegEvaluator:
 
     def __init__(self, dataset_name: Optional[str] = None, distributed: bool = True, output_dir=None, *,
                  class_names: Optional[Sequence[str]] = None, ignore_label: Optional[int] = None,
-                 gt_loader: Optional[Callable] = None, device=None):
+                 gt_loader: Optional[Callable] = None, device=None, rle: str = "device"):
+        if rle not in ("device", "host"):
+            raise ValueError(f"SemSegEvaluator: rle must be 'device' or 'host', got {rle!r}")
+        self._rle = rle
         meta = _metadata(dataset_name)
         if class_names is None:
             class_names = meta.get("stuff_classes") if meta is not None else None
@@ -206,9 +254,11 @@ class SemSegEvaluator:
                 raise ValueError(f"gt {tuple(gt.shape)} vs prediction {tuple(probs.shape[1:])}")
             ops.semseg_confusion(probs, gt, self._conf, self._invalid, num_classes=self._num_classes,
                                  ignore_label=self._ignore_label, clamp_pred=self.clamp_pred)
-            if self._output_dir:
-                # the records are written only with an output_dir, so only then is the argmax map
-                # brought to the host (the reference builds them for every image)
+            if self._output_dir and self._rle == "device":
+                # the records are written only with an output_dir (the reference builds them for every
+                # image); only the label runs of the argmax map are brought to the host
+                self._records_from_device(probs.argmax(dim=0).to(torch.int32), inp.get("file_name"))
+            elif self._output_dir:
                 pred = probs.argmax(dim=0)
                 if self.clamp_pred >= 0:
                     pred = pred.clamp(max=self.clamp_pred)
@@ -223,11 +273,34 @@ class SemSegEvaluator:
             raise ValueError(f"gt {tuple(gt.shape)} vs label map {tuple(labels.shape)}")
         ops.semseg_confusion_labels(labels, gt, self._conf, self._invalid, num_classes=self._num_classes,
                                     ignore_label=self._ignore_label, clamp_pred=self.clamp_pred)
-        if self._output_dir:
+        if self._output_dir and self._rle == "device":
+            self._records_from_device(labels, inp.get("file_name"))
+        elif self._output_dir:
             pred = labels.to(torch.int64)
             if self.clamp_pred >= 0:
                 pred = pred.clamp(max=self.clamp_pred)
             self._predictions.extend(self.encode_json_sem_seg(pred.cpu().numpy(), inp.get("file_name")))
+
+    def _records_from_device(self, labels, input_file_name):
+        """rle="device": the label runs of an int32 device label map (ops.label_runs, the clamp_pred fold
+        applied there) cross to the host, and the records are assembled from them."""
+        H, W = labels.shape
+        run_start, run_label = ops.label_runs(labels, clamp_pred=self.clamp_pred)
+        self._predictions.extend(self.encode_json_label_runs(run_start.cpu().numpy(), run_label.cpu().numpy(),
+                                                             H, W, input_file_name))
+
+    def _dataset_id(self, label) -> int:
+        if self._contiguous_id_to_dataset_id is None:
+            return int(label)
+        if int(label) not in self._contiguous_id_to_dataset_id:
+            raise AssertionError(f"Label {label} is not in the metadata info for {self._dataset_name}")
+        return self._contiguous_id_to_dataset_id[int(label)]
+
+    def encode_json_label_runs(self, run_start, run_label, H, W, input_file_name) -> list:
+        """encode_json_sem_seg from the column-major label runs of the argmax map (numpy arrays, as
+        ops.label_runs makes them on the device) instead of the map: the same records in the same order."""
+        return [{"file_name": input_file_name, "category_id": self._dataset_id(label), "segmentation": rle}
+                for label, rle in rle_records_from_runs(run_start, run_label, H, W)]
 
     def encode_json_sem_seg(self, sem_seg: np.ndarray, input_file_name) -> list:
         """COCO-stuff records of one argmax map (plain_train_net.py:207-228): one per label present,
@@ -235,13 +308,7 @@ class SemSegEvaluator:
         metadata has stuff_dataset_id_to_contiguous_id."""
         records = []
         for label in np.unique(sem_seg):
-            if self._contiguous_id_to_dataset_id is not None:
-                if int(label) not in self._contiguous_id_to_dataset_id:
-                    raise AssertionError(f"Label {label} is not in the metadata info for {self._dataset_name}")
-                dataset_id = self._contiguous_id_to_dataset_id[int(label)]
-            else:
-                dataset_id = int(label)
-            records.append({"file_name": input_file_name, "category_id": dataset_id,
+            records.append({"file_name": input_file_name, "category_id": self._dataset_id(label),
                             "segmentation": coco_rle_encode(sem_seg == label)})
         return records
 

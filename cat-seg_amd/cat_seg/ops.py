@@ -851,3 +851,63 @@ def semseg_confusion_labels(labels, gt, conf, n_invalid, *, num_classes, ignore_
         call("catseg_semseg_confusion_labels", labels.data_ptr(), H, W, gt.data_ptr(), num_classes, ignore_label,
              clamp_pred, conf.data_ptr(), n_invalid.data_ptr(), _stream())
     return conf
+
+
+def _label_map_args(labels, what):
+    """(H, W, ld) of a 2-D int32 device label map whose rows are contiguous (a row-strided view is fine)."""
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise ValueError(f"{what}: labels must be a CUDA tensor")
+    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.numel() == 0:
+        raise ValueError(f"{what}: labels must be a non-empty 2-D int32 tensor, got {labels.dtype} "
+                         f"{tuple(labels.shape)}")
+    H, W = labels.shape
+    if W > 1 and labels.stride(1) != 1:
+        raise ValueError(f"{what}: the rows of labels must be contiguous (stride {labels.stride(1)})")
+    ld = labels.stride(0) if H > 1 else W
+    if ld < W:
+        raise ValueError(f"{what}: row stride {ld} < W = {W}")
+    return H, W, ld
+
+
+def label_runs_count(labels, *, clamp_pred=-1):
+    """Count + scan half of `label_runs` (catseg_label_runs_count): returns the int32 workspace tensor, whose
+    element 0 is the number of runs R (still on the device) and whose rest holds the write offsets."""
+    H, W, ld = _label_map_args(labels, "label_runs")
+    nbytes = L.load().catseg_label_runs_workspace(H, W)
+    if nbytes <= 0:
+        raise ValueError(f"label_runs: a {H} x {W} map needs H * W < 2^31")
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
+    with _rec("label_runs_count", 0, 4 * H * W + nbytes):
+        call("catseg_label_runs_count", labels.data_ptr(), H, W, ld, int(clamp_pred), ws.data_ptr(), nbytes, _stream())
+    return ws
+
+
+def label_runs_write(labels, ws, run_start, run_label, *, clamp_pred=-1):
+    """Write half of `label_runs` (catseg_label_runs_write): fills the first min(R, capacity) elements of the
+    int32 device tensors run_start / run_label, capacity = their common length; nothing is stored beyond it."""
+    H, W, ld = _label_map_args(labels, "label_runs")
+    for t in (run_start, run_label):
+        assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and (t.numel() <= 1 or t.stride(0) == 1)
+    assert ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous()
+    cap = min(run_start.numel(), run_label.numel())
+    with _rec("label_runs_write", 0, 4 * H * W + 8 * cap):
+        call("catseg_label_runs_write", labels.data_ptr(), H, W, ld, int(clamp_pred), ws.data_ptr(), ws.numel() * 4,
+             run_start.data_ptr(), run_label.data_ptr(), cap, _stream())
+    return run_start, run_label
+
+
+def label_runs(labels, *, clamp_pred=-1):
+    """The column-major label runs of a label map (catseg_label_runs_count / _write): with p = x * H + y and
+    labels >= clamp_pred folded to clamp_pred (clamp_pred < 0: no fold), a run starts at p = 0 and wherever
+    the folded label differs from the one at p - 1 (column x continues column x - 1).  labels: 2-D int32 CUDA
+    tensor, possibly a row-strided view.  Returns (run_start, run_label): int32 device tensors of exactly R
+    elements, starts ascending.  Every per-label COCO RLE of the map follows from them on the host
+    (evaluation.rle_records_from_runs).
+
+    Runs count + scan, reads R from the device (one synchronising 4-byte copy), allocates exactly R and runs the
+    write pass.  Not registered as a torch.ops.catseg.* custom op: the output size depends on the data."""
+    ws = label_runs_count(labels, clamp_pred=clamp_pred)
+    R = int(ws[0].item())
+    run_start = torch.empty(R, dtype=torch.int32, device=labels.device)
+    run_label = torch.empty(R, dtype=torch.int32, device=labels.device)
+    return label_runs_write(labels, ws, run_start, run_label, clamp_pred=clamp_pred)

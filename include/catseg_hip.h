@@ -567,6 +567,37 @@ int catseg_semseg_confusion_labels(const int32_t* labels, int64_t H, int64_t W, 
                                    int num_classes, int ignore_label, int clamp_pred, int64_t* conf,
                                    int64_t* n_invalid, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * catseg_label_runs_* — the column-major label runs of an int32 label map, from which the host
+ * assembles every per-label COCO RLE of the map.  Replaces the per-pixel host work of
+ * encode_json_sem_seg (plain_train_net.py:207-228: np.unique, one `sem_seg == label` mask per
+ * label, pycocotools mask.encode = maskApi.c rleEncode over the column-major pixels) with one
+ * pass on the device; only the runs cross to the host.
+ *   labels [H][W] int32, row stride ld >= W elements (catseg_postprocess_argmax's and
+ *   catseg_tiled_merge's layout); any int32 value is a label, compared as an integer.
+ *   p = x * H + y; fold(l) = (clamp_pred >= 0 && l >= clamp_pred) ? clamp_pred : l (the fold of
+ *   catseg_semseg_confusion_labels); a run starts at p == 0 and wherever fold(label(p)) !=
+ *   fold(label(p - 1)), the predecessor of (x, 0) being (x - 1, H - 1) as rleEncode sees it.
+ * Needs H * W < 2^31.  Deterministic: positions come from counts and an exclusive scan.
+ *
+ * catseg_label_runs_workspace  bytes of workspace for an (H, W) map (0 for a bad shape).
+ * catseg_label_runs_count      counts the runs per 64-row segment of a column and scans the
+ *     counts (separate launches on the stream).  Afterwards ((int32_t*)workspace)[0] = R, the
+ *     number of runs; the rest of the workspace holds the write offsets.  workspace: 16-byte
+ *     aligned device memory.  The caller reads R (a device-to-host copy of its own) and
+ *     allocates the outputs: there is no worst-case allocation (R can be H * W).
+ * catseg_label_runs_write      with the workspace catseg_label_runs_count left for the same
+ *     map and arguments: run_start[i] = p of run i (ascending), run_label[i] = its folded label,
+ *     for i < min(R, capacity).  Never stores at an index >= capacity, whatever the map or the
+ *     workspace holds; leaves the workspace (and R) as they are.
+ * ------------------------------------------------------------------------- */
+int64_t catseg_label_runs_workspace(int64_t H, int64_t W);
+int catseg_label_runs_count(const int32_t* labels, int64_t H, int64_t W, int64_t ld, int clamp_pred,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int catseg_label_runs_write(const int32_t* labels, int64_t H, int64_t W, int64_t ld, int clamp_pred,
+                            const void* workspace, int64_t workspace_bytes, int32_t* run_start,
+                            int32_t* run_label, int64_t capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
