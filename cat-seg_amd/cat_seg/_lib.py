@@ -263,6 +263,7 @@ _SIGS = {
     "catseg_postprocess_tta": [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp],
     "catseg_tile_crops": [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, vp],
     "catseg_tiled_merge": [vp] + [i32] * 15 + [vp, vp, vp, vp],
+    "catseg_tiled_blend": [vp] + [i32] * 16 + [vp, vp, vp, vp, vp],
     "catseg_avgpool_rows": [vp, i64, i32, i32, i32, i32, i32, vp, i32, vp],
     "catseg_upsample_add_rows": [vp, i64, i32, i32, i32, vp, i32, i32, i32, vp],
     "catseg_sliding_crops": [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp],

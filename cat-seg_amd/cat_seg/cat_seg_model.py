@@ -71,13 +71,16 @@ class CATSeg(nn.Module):
                  backbone_multiplier: float, clip_pretrained: str, arch: Optional[CatSegArch] = None,
                  dtype: str = "bf16", return_all_images: bool = True, synthetic_seed: int = 0,
                  vit_fp8: bool = False, graph: bool = True, output: str = "probs", tiled: bool = False,
-                 tiled_tile: int = 384, tiled_stride: int = 256, tiled_batch: int = 8, tta_merge: str = "host"):
+                 tiled_tile: int = 384, tiled_stride: int = 256, tiled_batch: int = 8, tta_merge: str = "host",
+                 tiled_window: str = "uniform", tiled_global: bool = False):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
         # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
         self.tiled = bool(tiled)
         self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
+        self.tiled_window, self.tiled_global = str(tiled_window), bool(tiled_global)
+        tiling.check_window(self.tiled_window, self.tiled_tile)      # an unknown WINDOW; "pyramid" with TILE > 2048
         if self.tiled:
             if sliding_window:
                 raise ValueError("CATSeg: MODEL.CATSEG_HIP.TILED and TEST.SLIDING_WINDOW are two ways to cut one image "
@@ -156,6 +159,8 @@ class CATSeg(nn.Module):
             "tiled_tile": int(tiled.get("TILE", 384)),
             "tiled_stride": int(tiled.get("STRIDE", 256)),
             "tiled_batch": int(tiled.get("BATCH", 8)),
+            "tiled_window": str(tiled.get("WINDOW", "uniform")),
+            "tiled_global": bool(tiled.get("GLOBAL", False)),
             "tta_merge": str(hip.get("TTA_MERGE", "host")) if hip else "host",
         }
 
@@ -480,7 +485,8 @@ class CATSeg(nn.Module):
                                      f"applies no resize)")
                 img = im.to(eng.device, torch.float32).contiguous()
                 out = eng.forward_tiled(img, self.output == "labels", tile=self.tiled_tile,
-                                        stride=self.tiled_stride, batch=self.tiled_batch)
+                                        stride=self.tiled_stride, batch=self.tiled_batch,
+                                        window=self.tiled_window, global_view=self.tiled_global)
                 if self.output == "labels":
                     results.append({"sem_seg_labels": out[0], "sem_seg_score": out[1]})
                 else:

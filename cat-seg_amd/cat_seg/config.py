@@ -207,4 +207,9 @@ def add_cat_seg_config(cfg):
     cfg.MODEL.CATSEG_HIP.TILED.TILE = 384
     cfg.MODEL.CATSEG_HIP.TILED.STRIDE = 256     # the reference's int(384 * (1 - 0.333))
     cfg.MODEL.CATSEG_HIP.TILED.BATCH = 8
+    # the window over every tile in the merge ("uniform", or "pyramid": w(l) = min(l + 1, t' - l) per axis, no
+    # step where a tile's cover begins or ends) and the reference's extra global view (the whole scene resized
+    # to the tile's extent, averaged with the tiles' merge); catseg_tiled_blend
+    cfg.MODEL.CATSEG_HIP.TILED.WINDOW = "uniform"
+    cfg.MODEL.CATSEG_HIP.TILED.GLOBAL = False
     return cfg

@@ -780,14 +780,19 @@ class CatSegEngine:
 
     # ------------------------------------------------------------------ tiled eval at native resolution
     def forward_tiled(self, image: torch.Tensor, labels: bool = False, *, tile: int = 384, stride: int = 256,
-                      batch: int = 8):
+                      batch: int = 8, window: str = "uniform", global_view: bool = False):
         """One scene of any size at its own resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling holds the
         grid): the tiles, row-major in groups of `batch`, through catseg_tile_crops -> head_logits as
         images of the tile's size, their logits kept for the tile rows the merge still needs (at most 3,
         moved down as rows retire), and one catseg_tiled_merge per step of tiling.merge_schedule.
         image fp32 (3, H, W) 0-255 on the device.  Returns probabilities (T, H, W) fp32, or with
         labels=True (labels (H, W) int32, score (H, W) fp32) without any (T, H, W) volume: beyond the image
-        and the outputs, 3 tile rows of logits and the group in flight are live, whatever H."""
+        and the outputs, 3 tile rows of logits and the group in flight are live, whatever H.
+        window "pyramid" tapers every tile towards its border and global_view adds the whole scene resized to
+        the tile's extent as one more view, averaged with the tiles' merge (catseg_tiled_blend; TILED.WINDOW /
+        TILED.GLOBAL): the global image is run before the first merge step and its logits, one tile's worth,
+        stay live for all steps.  A scene of a single tile has no global view (it would be the same image).
+        With the defaults the calls are catseg_tiled_merge's, as before."""
         from . import tiling
         if not 1 <= batch <= 32:
             raise ValueError(f"forward_tiled: TILED.BATCH must be in [1, 32] (catseg_tile_crops), got {batch}")
@@ -795,6 +800,7 @@ class CatSegEngine:
         dev = self.device
         H, W = int(image.shape[-2]), int(image.shape[-1])
         g = tiling.tile_grid(H, W, tile, stride)
+        tiling.check_window(window, (g.th, g.tw))
         d = max(self.arch.size_divisibility, 1)
         ch, cw = _round_up(g.th, d), _round_up(g.tw, d)      # the plain path's canvas of an image of (th, tw)
         nx = g.nx
@@ -803,7 +809,15 @@ class CatSegEngine:
         sizes = torch.tensor([[g.th, g.tw]] * min(batch, len(tiles)), dtype=torch.int32, device=dev)
         lab = torch.empty(H, W, device=dev, dtype=torch.int32) if labels else None
         sc = torch.empty(H, W, device=dev, dtype=_f32) if labels else None
-        probs = ring = crop = None
+        probs = ring = crop = glob = None
+        if global_view and g.ny * nx > 1:
+            # the scene resized (bilinear, not antialiased) to the tile's extent, on a tile's canvas
+            canvas = torch.zeros(1, 3, ch, cw, device=dev, dtype=_f32)
+            small = torch.empty(1, 3, g.th, g.tw, device=dev, dtype=_f32)
+            ops.resize_bilinear(image[None], small)
+            canvas[:, :, :g.th, :g.tw].copy_(small)
+            glob = self.head_logits(canvas, sizes[:1])[0].clone()
+        blend = window != "uniform" or glob is not None
         base = si = 0                                            # tile row in slot 0 of the ring; next step
         for i in range(0, len(tiles), batch):
             grp = tiles[i:i + batch]
@@ -832,8 +846,12 @@ class CatSegEngine:
                 while si < len(steps) and steps[si][0] + steps[si][1] - 1 <= r:      # tile row r is complete
                     row0, rows, y0, y1 = steps[si]
                     s = (row0 - base) * nx
-                    ops.tiled_merge(ring[s:s + rows * nx], g, (row0, rows), (y0, y1), crop=crop, probs=probs,
-                                    labels=lab, score=sc)
+                    if blend:
+                        ops.tiled_blend(ring[s:s + rows * nx], g, (row0, rows), (y0, y1), weights=window,
+                                        global_logits=glob, crop=crop, probs=probs, labels=lab, score=sc)
+                    else:
+                        ops.tiled_merge(ring[s:s + rows * nx], g, (row0, rows), (y0, y1), crop=crop, probs=probs,
+                                        labels=lab, score=sc)
                     si += 1
         assert si == len(steps)
         return (lab, sc) if labels else probs

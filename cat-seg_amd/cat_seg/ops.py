@@ -636,6 +636,46 @@ def tiled_merge(logits, geometry, window, rows, *, crop=None, probs=None, labels
     return probs, labels, score
 
 
+def tiled_blend(logits, geometry, window, rows, *, weights="uniform", global_logits=None, crop=None, probs=None,
+                labels=None, score=None):
+    """`tiled_merge` with a window over every tile and, optionally, a global view (catseg_tiled_blend): every
+    tile's value weighted by w(y - oy) * w(x - ox), w = tiling.window_weights(tile extent, weights), summed in
+    row-major tile order and scaled by 1 / sum(w); with global_logits (T, h, w) fp32, the logits of the whole
+    scene resized to the tile's extent, the result is 0.5 * (that + the `postprocess` of global_logits to
+    (H, W)).  weights="uniform" without global_logits is `tiled_merge` bit for bit.  The other arguments and
+    the return value are `tiled_merge`'s."""
+    from . import tiling
+    H, W, th, tw, sy, sx = (int(v) for v in tuple(geometry)[:6])
+    row0, nrows = (int(v) for v in window)
+    y0, y1 = (int(v) for v in rows)
+    n, T, h, w = logits.shape
+    ch, cw = crop if crop is not None else (h, w)
+    win = tiling.check_window(weights, (th, tw))
+    if probs is None and labels is None:
+        raise ValueError("tiled_blend: pass probs and / or labels")
+    nx = max(W - tw + sx - 1, 0) // sx + 1
+    if n != nrows * nx:
+        raise ValueError(f"tiled_blend: a window of {nrows} tile rows of {nx} tiles needs {nrows * nx} logits, "
+                         f"got {n}")
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    assert global_logits is None or (global_logits.dtype == torch.float32 and global_logits.is_contiguous()
+                                     and tuple(global_logits.shape[-3:]) == (T, h, w)
+                                     and global_logits.numel() == T * h * w)
+    assert probs is None or (probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == T * H * W)
+    assert labels is None or (labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == H * W)
+    assert score is None or (score.dtype == torch.float32 and score.is_contiguous() and score.numel() == H * W)
+    # the window's crops and the global view's read once (at most); the rows of the outputs written once
+    nbytes = 4 * (T * (n + (global_logits is not None)) * ch * cw
+                  + (y1 - y0) * W * ((T if probs is not None else 0)
+                                     + ((1 if score is None else 2) if labels is not None else 0)))
+    with _rec("tiled_blend", 0, nbytes):
+        call("catseg_tiled_blend", logits.data_ptr(), T, h, w, int(ch), int(cw), H, W, th, tw, sy, sx, row0, nrows,
+             y0, y1, win, 0 if global_logits is None else global_logits.data_ptr(),
+             0 if probs is None else probs.data_ptr(), 0 if labels is None else labels.data_ptr(),
+             0 if score is None else score.data_ptr(), _stream())
+    return probs, labels, score
+
+
 def avgpool_rows(x, out, *, S, H, W, C, pool):
     """nn.AvgPool2d(pool) over [S][H][W][C] rows -> out [S][H/ph][W/pw][C] (catseg_avgpool_rows)."""
     ph, pw = pool

@@ -80,6 +80,41 @@ def covering(origins, t: int, p: int) -> Tuple[int, int]:
     return idx[0], idx[-1]
 
 
+WINDOWS = ("uniform", "pyramid")                 # catseg_tiled_blend's window 0 / 1
+PYRAMID_MAX_TILE = 2048                          # sum(w) <= 2.25 t'^2 < 2^24: the fp32 weights stay exact
+
+
+def check_window(kind: str, tile=None) -> int:
+    """The kernel's code of a window kind; "pyramid" refuses a tile extent above PYRAMID_MAX_TILE."""
+    if kind not in WINDOWS:
+        raise ValueError(f"tiling: the window must be one of {WINDOWS}, got {kind!r}")
+    if kind == "pyramid" and tile is not None and max(_pair(tile)) > PYRAMID_MAX_TILE:
+        raise ValueError(f"tiling: the pyramid window needs a tile extent of at most {PYRAMID_MAX_TILE} (its weights "
+                         f"must sum below 2^24 to be exact in fp32), got {tile}")
+    return WINDOWS.index(kind)
+
+
+def window_weights(t: int, kind: str) -> List[int]:
+    """The weights w(l), l = 0 .. t-1, of one axis of a tile of extent t (the t' of the grid): "uniform" 1,
+    "pyramid" min(l + 1, t - l).  Integers, at least 1 everywhere.  A pixel of tile i has the weight
+    w(y - oy_i) * w(x - ox_i); the merge is sum(w_i p_i) / sum(w_i) over the covering tiles
+    (csrc/post_tiled.hip: catseg_tiled_blend evaluates the same integers)."""
+    check_window(kind)
+    t = int(t)
+    return [min(l + 1, t - l) if kind == "pyramid" else 1 for l in range(t)]
+
+
+def weight_sum(origins, t: int, L: int, kind: str) -> List[int]:
+    """sum of w(p - o_i) over the tiles of one axis that cover p, for p = 0 .. L-1.  A pixel's sum(w_i) is
+    the product of its two axes' sums."""
+    w = window_weights(t, kind)
+    out = [0] * int(L)
+    for o in origins:
+        for l in range(int(t)):
+            out[o + l] += w[l]
+    return out
+
+
 def merge_schedule(H: int, th: int, sy: int) -> Iterator[Tuple[int, int, int, int]]:
     """Steps (row0, rows, y0, y1) of a streaming merge: output rows [y0, y1) are final once tile rows
     row0 .. row0 + rows - 1 are known.  The [y0, y1) ranges partition [0, H) in order, each window holds

@@ -439,6 +439,28 @@ int catseg_tiled_merge(const float* logits, int T, int h, int w, int crop_h, int
                        int H, int W, int th, int tw, int sy, int sx, int row0, int rows,
                        int y0, int y1, float* probs, int32_t* labels, float* score, void* stream);
 
+/* catseg_tiled_blend — catseg_tiled_merge with a window over every tile and, optionally, a global view;
+ * every argument it shares with catseg_tiled_merge means the same and is checked the same.
+ *   window 0 ("uniform"): w(l) = 1;  window 1 ("pyramid"): w(l) = min(l + 1, t' - l) for local coordinate l of
+ *   an axis of tile extent t' (cat_seg/tiling.py: window_weights), an integer >= 1; needs th, tw <= 2048
+ *   w_i = w(y - oy_i) * w(x - ox_i), an integer product converted to fp32 (exact: the sums stay below 2^24)
+ *   s = 0; s = s + (w_i * p_i) over the covering tiles in row-major tile order: a multiply, then an add (two
+ *   roundings, never one fma);  m = s * (1.0f / (float)sum(w)), sum(w) = (sum of w_y over the covering tile
+ *   rows) * (sum of w_x over the covering tile columns), an integer product
+ * global_logits fp32 [T][h][w] or NULL: the logits of the whole scene resized to the tile's extent (th, tw),
+ * of the tiles' shape and crop.  With them
+ *   g(t, y, x) = the value catseg_postprocess forms for them with (crop_h, crop_w) -> (H, W)
+ *   out = 0.5f * (m + g): an add, then an exact halving (the reference's (outputs + global_output) / 2.)
+ * else out = m.  probs[t][y][x] = out;  labels[y][x] = first maximum of out over t;  score[y][x] = that
+ * maximum; NaN as catseg_tiled_merge.  window 0 without global_logits is catseg_tiled_merge bit for bit.
+ * The source patch of one 16 x 64 output tile must fit the 4096-float LDS stage for a tile and for the global
+ * view; the error names the view(s) that do not (with th <= H and tw <= W the global view's patch never
+ * exceeds a tile's). */
+int catseg_tiled_blend(const float* logits, int T, int h, int w, int crop_h, int crop_w,
+                       int H, int W, int th, int tw, int sy, int sx, int row0, int rows,
+                       int y0, int y1, int window, const float* global_logits,
+                       float* probs, int32_t* labels, float* score, void* stream);
+
 /* ---------------------------------------------------------------------------
  * catseg_swin_window_attention — fused LayerNorm(norm1) + [q|k|v] projection (+ the
  * per-image guidance half of q and k) + shifted-window multi-head attention, one
