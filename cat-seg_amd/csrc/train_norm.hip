@@ -471,10 +471,13 @@ __global__ __launch_bounds__(256) void upsample_ac_bwd_kernel(const float* __res
   const int64_t pix = i / c4n;
   const int qx = (int)(pix % Wp), qy = (int)((pix / Wp) % Hp);
   const int64_t s = pix / ((int64_t)Hp * Wp);
-  // fine rows whose taps can reach qy: src in (qy - 1, qy + 1]
+  // fine rows whose taps can reach qy: src in (qy - 1, qy + 1]; a one-row coarse grid has no inverse
+  // scale (ac_taps sends every fine row to row 0 with weight 1): its window is all rows
   const float sy = Hp > 1 ? (float)(H - 1) / (float)(Hp - 1) : 0.f, sx = Wp > 1 ? (float)(W - 1) / (float)(Wp - 1) : 0.f;
   int ylo = (int)floorf((float)(qy - 1) * sy) - 1, yhi = (int)ceilf((float)(qy + 1) * sy) + 1;
   int xlo = (int)floorf((float)(qx - 1) * sx) - 1, xhi = (int)ceilf((float)(qx + 1) * sx) + 1;
+  if (Hp == 1) { ylo = 0; yhi = H - 1; }
+  if (Wp == 1) { xlo = 0; xhi = W - 1; }
   ylo = ylo < 0 ? 0 : ylo; xlo = xlo < 0 ? 0 : xlo;
   yhi = yhi > H - 1 ? H - 1 : yhi; xhi = xhi > W - 1 ? W - 1 : xhi;
   float4 acc = make_float4(0, 0, 0, 0);

@@ -119,7 +119,8 @@ int catseg_sum_pixels(const float* x, int64_t ld_x, int64_t B, int T, int64_t HW
 int catseg_avgpool_backward_rows(const float* dxp, int64_t S, int H, int W, int C, int ph, int pw, float* dx, int beta,
                                  void* stream);
 /* catseg_upsample_ac_backward_rows — backward of bilinear(align_corners=True) [S][Hp][Wp][C] ->
- * [S][H][W][C] (model.py:415-416), gather form (no atomics). */
+ * [S][H][W][C] (model.py:415-416), gather form (no atomics).  Any Hp, Wp >= 1, smaller or larger than
+ * H, W; a one-entry coarse axis collects every fine row (column) with weight 1.  C % 4 == 0. */
 int catseg_upsample_ac_backward_rows(const float* dy, int64_t S, int H, int W, int C, int Hp, int Wp, float* dxp,
                                      int beta, void* stream);
 /* catseg_convt_gather — the gradient of a ConvTranspose2d(k, stride k) output [S][hin*k][win*k] (pixel

@@ -171,6 +171,28 @@ def check_pair_flat(dense, poisoned, shape, what, values=None, identical=True):
         check_bit_identical(dense[:n], poisoned[:n], f"{what}: dense vs poisoned run")
 
 
+def check_pair_rows(dense, poisoned, rows_idx, cols, what, values=None, identical=True):
+    """check_pair for outputs whose rows a row map or an index names (scatter stores, row-mapped kernels):
+    the result is rows `rows_idx` (a 1-D index tensor) x [:cols] of each 2-D buffer; every other row, like
+    the padding, must still hold the sentinel."""
+    res = []
+    for tag, buf in (("dense", dense), ("poisoned", poisoned)):
+        assert buf.dim() == 2
+        ok = holds_fill(buf).clone()
+        ok[rows_idx, :cols] = True
+        if not bool(ok.all()):
+            r, c = _first(~ok)
+            kind = "a padding column" if c >= cols else "a row the index does not name"
+            raise AssertionError(f"{what} [{tag}]: {kind} was written: first at row {r}, column {c}")
+        got = buf[rows_idx, :cols]
+        check_no_nan(got, f"{what} [{tag}]")
+        if values is not None:
+            values(got, f"{what} [{tag}]")
+        res.append(got)
+    if identical:
+        check_bit_identical(res[0], res[1], f"{what}: dense vs poisoned run")
+
+
 @contextlib.contextmanager
 def knobs(**kw):
     """Set tuning knobs for the block and put their previous values back afterwards."""

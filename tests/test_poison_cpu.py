@@ -124,6 +124,37 @@ def test_flat_form_and_bit_patterns():
             P.check_no_nan(b[3:4, :4], "pattern")
 
 
+def test_row_indexed_form():
+    """check_pair_rows: a scatter of 3 rows into 6 (dense) and into a padded 8 x 12 buffer, then the same scatter
+    with a store to a row the index does not name, to a padding column, and with an element left unwritten."""
+    idx = torch.tensor([4, 0, 3])
+    x = torch.rand(3, 4, generator=torch.Generator().manual_seed(1))
+
+    def scatter(pad, extra=None, skip=None):
+        buf, view = P.out_buffer(6, 4, 2 if pad else 0, 8 if pad else 0, F32, device="cpu")
+        view[idx] = x
+        if skip is not None:
+            view[skip] = P.NAN
+        if extra is not None:
+            buf[extra] = 1.0
+        return buf
+
+    def values(got, what):
+        assert torch.equal(got, x), what
+
+    P.check_pair_rows(scatter(False), scatter(True), idx, 4, "scatter", values)
+    with pytest.raises(AssertionError, match=r"\[poisoned\]: a row the index does not name was written: first at row 2, column 1"):
+        P.check_pair_rows(scatter(False), scatter(True, extra=(2, 1)), idx, 4, "scatter", values)
+    with pytest.raises(AssertionError, match=r"\[poisoned\]: a padding column was written: first at row 4, column 4"):
+        P.check_pair_rows(scatter(False), scatter(True, extra=(4, 4)), idx, 4, "scatter", values)
+    with pytest.raises(AssertionError, match=r"\[dense\]: 1 NaN / sentinel element\(s\) in the result"):
+        P.check_pair_rows(scatter(False, skip=(3, 2)), scatter(True), idx, 4, "scatter")
+    other = scatter(True)
+    other[0, 0] = -other[0, 0]
+    with pytest.raises(AssertionError, match="differ in bits"):
+        P.check_pair_rows(scatter(False), other, idx, 4, "scatter")
+
+
 def test_close_names_nan():
     with pytest.raises(AssertionError, match="1 NaN element"):
         P.close(torch.tensor([1.0, P.NAN]), torch.tensor([1.0, 2.0]), atol=1.0, what="x")
