@@ -312,6 +312,10 @@ _SIGS = {
     "catseg_head_conv_backward_workspace": [i64, i32, i32, i32],
     "catseg_vpt_rows_forward": [vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp],
     "catseg_vpt_rows_backward": [vp, i64, vp, i64, i64, i32, i32, i32, i32, vp],
+    "catseg_class_inverse": [vp, i64, i32, i32, vp, vp],
+    "catseg_class_rows_reduce": [vp, i64, vp, i64, i32, i32, i64, vp, i64, i32, vp],
+    "catseg_class_planes_gather": [vp, i64, i64, vp, i64, i32, i32, i64, vp, i64, i64, vp],
+    "catseg_class_planes_scatter": [vp, i64, i64, vp, i64, i32, i32, i64, f32, vp, i64, i64, vp],
     "catseg_abi_version": [],
     "catseg_last_error": [],
 }

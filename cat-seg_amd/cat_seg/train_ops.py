@@ -217,6 +217,77 @@ def vpt_rows_backward(dx, dprompt, *, B, L0, P, beta=0):
     return dprompt
 
 
+def _idx_chk(t, *shape):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape, \
+        (t.dtype, t.device, tuple(t.shape), shape)
+
+
+def _planes(t):
+    """(b_stride, t_stride) of a [B][n][...] plane view whose planes are contiguous."""
+    assert t.dim() >= 3, tuple(t.shape)
+    P = 1
+    for n, s in zip(reversed(t.shape[2:]), reversed(t.stride()[2:])):
+        assert n == 1 or s == P, (tuple(t.shape), t.stride())
+        P *= n
+    return t.stride(0), t.stride(1), P
+
+
+def class_inverse(classes, T0, out=None):
+    """inv (B, T0) int32: the position of class t in classes[b] (B, k) or -1 (catseg_class_inverse)."""
+    B, k = classes.shape
+    _idx_chk(classes, B, k)
+    if out is None:
+        out = torch.empty(B, T0, device=classes.device, dtype=torch.int32)
+    _idx_chk(out, B, T0)
+    call("catseg_class_inverse", classes.data_ptr(), B, k, T0, out.data_ptr(), _stream())
+    return out
+
+
+def class_rows_reduce(d, inv, out, *, k, beta=0):
+    """out[t] (+)= sum_b d[b*k + inv[b][t]] over the images that selected class t, ascending b
+    (catseg_class_rows_reduce).  d (B*k, cols), out (T0, cols) row views, inv (B, T0)."""
+    _chk(d, out)
+    B, T0 = inv.shape
+    _idx_chk(inv, B, T0)
+    cols = out.shape[1]
+    assert d.shape == (B * k, cols) and out.shape[0] == T0 and d.stride(1) == 1 and out.stride(1) == 1
+    with _rec("class_rows_reduce", 0, 4 * (B * k + T0) * cols):
+        call("catseg_class_rows_reduce", d.data_ptr(), d.stride(0), inv.data_ptr(), B, k, T0, cols, out.data_ptr(),
+             out.stride(0), int(beta), _stream())
+    return out
+
+
+def class_planes_gather(x, classes, out):
+    """out[b][j] = x[b][classes[b][j]] (catseg_class_planes_gather).  x (B, T0, ...), out (B, k, ...) views
+    with contiguous planes, classes (B, k)."""
+    _chk(x, out)
+    B, k = classes.shape
+    _idx_chk(classes, B, k)
+    xb, xt, P = _planes(x)
+    ob, ot, Po = _planes(out)
+    assert x.shape[0] == B and out.shape[:2] == (B, k) and P == Po, (tuple(x.shape), tuple(out.shape))
+    with _rec("class_planes_gather", 0, 8 * B * k * P):
+        call("catseg_class_planes_gather", x.data_ptr(), xt, xb, classes.data_ptr(), B, k, x.shape[1], P,
+             out.data_ptr(), ot, ob, _stream())
+    return out
+
+
+def class_planes_scatter(x, inv, out, fill):
+    """out[b][t] = x[b][inv[b][t]] where inv[b][t] >= 0, else fill (catseg_class_planes_scatter).
+    x (B, k, ...), out (B, T0, ...) views with contiguous planes, inv (B, T0)."""
+    _chk(x, out)
+    B, T0 = inv.shape
+    _idx_chk(inv, B, T0)
+    xb, xt, P = _planes(x)
+    ob, ot, Po = _planes(out)
+    k = x.shape[1]
+    assert x.shape[0] == B and out.shape[:2] == (B, T0) and P == Po, (tuple(x.shape), tuple(out.shape))
+    with _rec("class_planes_scatter", 0, 4 * B * (k + T0) * P):
+        call("catseg_class_planes_scatter", x.data_ptr(), xt, xb, inv.data_ptr(), B, k, T0, P, float(fill),
+             out.data_ptr(), ot, ob, _stream())
+    return out
+
+
 def sum_classes(x, out, *, B, T, HW, C_, beta=0):
     """out[b*HW + p] (+)= sum_t x[(b*T + t)*HW + p] over the first C_ columns (catseg_sum_classes)."""
     _chk(x, out)

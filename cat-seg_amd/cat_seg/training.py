@@ -7,6 +7,9 @@ kernels of libcatseg_hip.so (forward: catseg_hip.h, backward: catseg_hip_train.h
 
   ConvTUpsample   CATSeg.upsample1/2 ConvTranspose2d (cat_seg_model.py:81-82,184-185)
   CostVolume      Aggregator.correlation (model.py:648-652)
+  CostVolumeTopk / GatherClassRows / ScatterClassPlanes
+                  more classes than pad_len: the per-image top-k selection, the gathered text rows and
+                  the -100 scatter of the output (model.py:693-702,712-715,721-724)
   CorrEmbed       conv1 7x7 (model.py:613,654-659)
   Conv3x3         guidance projections + ReLU (model.py:615-630,706-711)
   L2Norm / Linear text guidance (model.py:712-715)
@@ -40,6 +43,10 @@ from .arch import CatSegArch
 from .weights import AGG
 
 _f32 = torch.float32
+
+# the class selection (B, pad_len) int32 of the last head_train_forward with more classes than pad_len, a
+# device tensor (nothing reads it on the host here), None otherwise: as CatSegEngine.last_topk at eval
+last_topk: Optional[torch.Tensor] = None
 
 
 def _empty(*shape, like):
@@ -277,6 +284,103 @@ class CostVolumeFn(torch.autograd.Function):
         return dfeats, dtext, None
 
 
+class CostVolumeTopkFn(torch.autograd.Function):
+    """The cost volume with more classes than pad_len (model.py:693-702): the full corr over the T0
+    classes as CostVolumeFn, classes = the k = pad_len classes of largest max over the pixels per image
+    (catseg_topk_classes; not differentiable), and the cost volume of the gathered normalized text rows,
+    which is the k selected planes of corr.  Returns (corr_sel [B][k][HW], classes [B][k] int32,
+    inv [B][T0] int32 = the position of a class in its image's selection or -1); classes and inv stay on
+    the device.  Backward on the selected planes only (K = k): gradient reaches the image features and
+    the text through the selected rows alone, nothing flows through the max or the top-k."""
+
+    @staticmethod
+    def forward(ctx, feats, text, HW, k):
+        feats, text = feats.contiguous(), text.contiguous()
+        B = feats.shape[0] // (HW + 1)
+        T0, Co = text.shape
+        drop_cls = rowmap(d1=HW, s1=HW + 1, d2=1, m2=HW, s2=1, off=1)
+        fn = _empty(B * HW, Co, like=feats)
+        ops.l2normalize(feats, fn, inmap=drop_cls)
+        txn = torch.empty_like(text)
+        ops.l2normalize(text, txn)
+        corr = _empty(B, T0, HW, like=feats)
+        for b in range(B):
+            ops.gemm(txn, fn[b * HW:(b + 1) * HW], corr[b])
+        classes = torch.empty(B, k, device=feats.device, dtype=torch.int32)
+        ops.topk_classes(corr, t_stride=HW, b_stride=T0 * HW, B=B, T=T0, HW=HW, k=k, out=classes)
+        inv = TO.class_inverse(classes, T0)
+        sel = TO.class_planes_gather(corr, classes, _empty(B, k, HW, like=feats))
+        ctx.save_for_backward(feats, text, fn, txn, classes, inv)
+        ctx.HW = HW
+        ctx.mark_non_differentiable(classes, inv)
+        return sel, classes, inv
+
+    @staticmethod
+    def backward(ctx, dsel, _dclasses, _dinv):
+        feats, text, fn, txn, classes, inv = ctx.saved_tensors
+        HW = ctx.HW
+        B, k = classes.shape
+        T0, Co = text.shape
+        dsel = dsel.contiguous()
+        dfeats = dtext = None
+        if ctx.needs_input_grad[0]:
+            txn_sel = ops.gather_rows(txn, classes.reshape(-1), _empty(B * k, Co, like=text))
+            dfn = _empty(B * HW, Co, like=feats)
+            for b in range(B):      # d fn[b] = dcorr_sel[b]^T . txn_sel[b]
+                TO.gemm_ex(dsel[b], 1, HW, txn_sel[b * k:(b + 1) * k], Co, 1, dfn[b * HW:(b + 1) * HW], M=HW, N=Co, K=k)
+            dfeats = torch.zeros_like(feats)
+            m = rowmap(d1=HW, s1=HW + 1, d2=1, m2=HW, s2=1, off=1)
+            TO.l2normalize_backward(feats, dfn, dfeats, rows=B * HW, cols=Co, inmap=m, outmap=m)
+        if ctx.needs_input_grad[1]:
+            dtxn_sel = _empty(B * k, Co, like=text)
+            for b in range(B):      # d txn_sel[b] = dcorr_sel[b] . fn[b]
+                TO.gemm_ex(dsel[b], HW, 1, fn[b * HW:(b + 1) * HW], Co, 1, dtxn_sel[b * k:(b + 1) * k], M=k, N=Co, K=HW)
+            dtxn = TO.class_rows_reduce(dtxn_sel, inv, _empty(T0, Co, like=text), k=k)
+            dtext = torch.empty_like(text)
+            TO.l2normalize_backward(text, dtxn, dtext, rows=T0, cols=Co)
+        return dfeats, dtext, None, None
+
+
+class GatherClassRowsFn(torch.autograd.Function):
+    """Rows gathered per image: x [T0][C] -> [B*k][C], row b*k + j = x[classes[b][j]] (the text guidance of
+    the selected classes, model.py:698,712-715: the row-wise mean / normalize / projection commute with
+    the gather, so they run once on all T0 rows).  Backward: catseg_class_rows_reduce through inv."""
+
+    @staticmethod
+    def forward(ctx, x, classes, inv):
+        x = x.contiguous()
+        B, k = classes.shape
+        ctx.save_for_backward(inv)
+        ctx.k = k
+        return ops.gather_rows(x, classes.reshape(-1), _empty(B * k, x.shape[1], like=x))
+
+    @staticmethod
+    def backward(ctx, d):
+        (inv,) = ctx.saved_tensors
+        d = d.contiguous()
+        return TO.class_rows_reduce(d, inv, _empty(inv.shape[1], d.shape[1], like=d), k=ctx.k), None, None
+
+
+class ScatterClassPlanesFn(torch.autograd.Function):
+    """out = full((B, T0, h, w), -100.); out.scatter_(1, classes, logit) (model.py:722-723) in one pass
+    (catseg_class_planes_scatter).  Backward: the gather of the selected planes; unselected planes pass
+    no gradient."""
+
+    @staticmethod
+    def forward(ctx, logit, classes, inv):
+        logit = logit.contiguous()
+        B, T0 = inv.shape
+        ctx.save_for_backward(classes)
+        return TO.class_planes_scatter(logit, inv, _empty(B, T0, *logit.shape[2:], like=logit), -100.0)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (classes,) = ctx.saved_tensors
+        dout = dout.contiguous()
+        B, k = classes.shape
+        return TO.class_planes_gather(dout, classes, _empty(B, k, *dout.shape[2:], like=dout)), None, None
+
+
 class CorrEmbedFn(torch.autograd.Function):
     """Aggregator.corr_embed: Conv2d(1, D, 7, pad 3) per (image, class) cost slice (model.py:654-659).
     corr [B][T][G*G] -> X rows [B*T*G*G][D]."""
@@ -430,7 +534,8 @@ class ClassLayerFn(torch.autograd.Function):
     """ClassTransformerLayer.forward (model.py:387-424): x_pool = AvgPool(x), padded with the learned
     padding token / guidance to pad_len classes (model.py:397-410); x_pool += Attn(LN1(x_pool),
     text guidance), Attn = LinearAttention or FullAttention by geo.attn (model.py:331-334); x_pool += MLP(LN2(x_pool)); x + bilinear_align_corners(x_pool) cropped to T.
-    X rows [B*T*HW][D], tg [T][Dt] (text_guidance_projection output, shared by the images)."""
+    X rows [B*T*HW][D], tg [T][Dt] (text_guidance_projection output, shared by the images) or, with the
+    top-k class selection (model.py:694-702: T = pad_len, no padding tokens), [B*T][Dt] per image."""
 
     @staticmethod
     def forward(ctx, X, tg, geo, pool, pad_len, n1w, n1b, qw, qb, kw, kb, vw, vb, n2w, n2b, w0, b0, w2, b2,
@@ -451,10 +556,15 @@ class ClassLayerFn(torch.autograd.Function):
         wx, bx, wt = _qkv_split(qw, qb, kw, kb, vw, vb, D)
         h = torch.empty_like(Xp)
         ops.layernorm(Xp, n1w.detach(), n1b.detach(), h)
-        tgqk = _empty(geo.T, 2 * D, like=X)
+        # tg: the T classes' guidance shared by the images, or with top-k selection each image's own k rows
+        # [B*T][Dt] (model.py:698-701; one image: the same thing)
+        per_image = tg.shape[0] != geo.T
+        assert tg.shape[0] == (S if per_image else geo.T), (tuple(tg.shape), geo)
+        tgqk = _empty(tg.shape[0], 2 * D, like=X)
         ops.gemm(tg, wt, tgqk)
         qkv = _empty(Rp, 3 * D, like=X)
-        ops.gemm(h, wx, qkv, bias=bx, add=tgqk, addmap=rowmap(d1=HWc, m1=geo.T), add_ncols=2 * D)
+        ops.gemm(h, wx, qkv, bias=bx, add=tgqk, addmap=rowmap(d1=HWc) if per_image else rowmap(d1=HWc, m1=geo.T),
+                 add_ncols=2 * D)
         n_pad = pad_len - geo.T if pad_len > 0 and geo.T < pad_len else 0
         hp = kvp = None
         if n_pad:
@@ -532,8 +642,10 @@ class ClassLayerFn(torch.autograd.Function):
         dn1w, dn1b = _empty(D, like=Xp), _empty(D, like=Xp)
         TO.layernorm_backward(Xp, n1w.detach(), dh, dXp, acc_dx=True, dgamma=dn1w, dbeta=dn1b)
         # text-guidance halves of q, k: broadcast over images and pixels
-        dtqk = _empty(geo.T, 2 * D, like=Xp)
-        TO.sum_pixels(dqkv, dtqk, B=geo.B, T=geo.T, HW=HWc, C_=2 * D)
+        # (per-image guidance: one row per (image, class), summed over the pixels only)
+        per_image = tg.shape[0] != geo.T
+        dtqk = _empty(tg.shape[0], 2 * D, like=Xp)
+        TO.sum_pixels(dqkv, dtqk, B=1 if per_image else geo.B, T=tg.shape[0], HW=HWc, C_=2 * D)
         dwt = _mm_t(dtqk, tg)
         dtg = TO.mm(dtqk, wt) if ctx.needs_input_grad[1] else None
         dpad_tok = dpad_guid = None
@@ -1020,16 +1132,18 @@ def head_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], feats: torc
     model.py:683-725), fp32, with the HIP backward.  P: parameters by reference key (nn.Parameters
     of the model); feats [B*(1+G^2)][C_o] dense CLIP tokens, hooks 2 x [B*(1+G^2)][W_v] (the forward
     hooks of cat_seg_model.py:84-87; with visual prompt tuning both without the prompt rows, which every
-    block drops from its output, model_vpt.py:215-216), text [T][C_o] class embeddings.  Returns logits [B][T][4G][4G]."""
+    block drops from its output, model_vpt.py:215-216), text [T][C_o] class embeddings.  Returns logits [B][T][4G][4G].
+    With T > pad_len the head runs on each image's pad_len classes of largest cost (model.py:694-702) and
+    the other classes' planes are -100 (model.py:721-724); the selection stays on the device (`last_topk`)."""
     a = arch
     if a.attention_type not in ("linear", "full"):
         raise NotImplementedError(f"training step: unknown ATTENTION_TYPE {a.attention_type!r}")
     G = a.grid
     HW = G * G
     B = feats.shape[0] // (HW + 1)
-    T = text.shape[0]
-    if a.pad_len > 0 and T > a.pad_len:
-        raise NotImplementedError("training with more classes than pad_len (top-k selection) is not built")
+    T0 = text.shape[0]
+    topk = a.pad_len > 0 and T0 > a.pad_len         # model.py:694: the head runs on pad_len classes per image
+    T = a.pad_len if topk else T0
     if a.hidden_dim != 128 or a.nheads != 4:
         raise NotImplementedError("HIP training path: hidden_dim 128 / 4 heads only")
     geo = Geo(B=B, T=T, H=G, W=G, nh=a.nheads, attn=a.attention_type)
@@ -1039,7 +1153,13 @@ def head_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], feats: torc
     res4 = ConvTUpsampleFn.apply(hooks[0], P["upsample1.weight"], P["upsample1.bias"], G)
     res5 = ConvTUpsampleFn.apply(hooks[1], P["upsample2.weight"], P["upsample2.bias"], G)
     # cost volume + embedding (model.py:648-659,689-699)
-    corr = CostVolumeFn.apply(feats, text, HW)
+    global last_topk
+    classes = inv = None
+    if topk:
+        corr, classes, inv = CostVolumeTopkFn.apply(feats, text, HW, T)
+    else:
+        corr = CostVolumeFn.apply(feats, text, HW)
+    last_topk = classes
     X = CorrEmbedFn.apply(corr, P[p + "conv1.weight"], P[p + "conv1.bias"], G)
     # guidance projections (model.py:706-715)
     g3 = Conv3x3Fn.apply(res3, P[p + "guidance_projection.0.weight"], P[p + "guidance_projection.0.bias"], B, G, G)
@@ -1049,6 +1169,8 @@ def head_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], feats: torc
     tn = L2NormFn.apply(text)          # text_feats.mean over prompts (one) then normalized again (model.py:712-714)
     tg = LinearFn.apply(tn, P[p + "text_guidance_projection.0.weight"], P[p + "text_guidance_projection.0.bias"],
                         L.ACT_RELU)
+    if topk:        # each image's own k rows (model.py:698-701,712-715), [B*k][Dt]
+        tg = GatherClassRowsFn.apply(tg, classes, inv)
     ws = a.window_size
     shift2 = ws // 2
     if min(G, G) <= ws:
@@ -1076,4 +1198,7 @@ def head_train_forward(arch: CatSegArch, P: Dict[str, torch.Tensor], feats: torc
             "conv.double_conv.1.bias", "conv.double_conv.3.weight", "conv.double_conv.4.weight",
             "conv.double_conv.4.bias")))
         h *= 2
-    return HeadConvFn.apply(y, P[p + "head.weight"], P[p + "head.bias"], geo, h)
+    logits = HeadConvFn.apply(y, P[p + "head.weight"], P[p + "head.bias"], geo, h)
+    if topk:        # model.py:721-724: -100 everywhere, the k planes scattered to their classes
+        logits = ScatterClassPlanesFn.apply(logits, classes, inv)
+    return logits

@@ -157,6 +157,40 @@ int catseg_vpt_rows_backward(float* dx, int64_t ld_dx, float* dprompt, int64_t l
                              int W, int beta, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Training with more classes than pad_len: the per-image top-k class selection of Aggregator.forward
+ * (model.py:691-725; the selection itself is catseg_topk_classes).  B images, T0 classes, k = pad_len
+ * selected per image; every entry needs 0 < k <= T0 <= 2048 (the limit of catseg_topk_classes) and
+ * refuses null pointers and non-positive sizes before any launch.  fp32, no atomics, every output
+ * element written once per call; 16-byte accesses when the lengths, strides and bases allow, a scalar
+ * path otherwise.  Inputs must not overlap outputs.
+ * ------------------------------------------------------------------------- */
+/* catseg_class_inverse — inv[b][t] = the position j of class t in classes[b][0..k) or -1: the index the
+ * backward passes read contributions through (model.py:696 `classes`, inverted).  One workgroup per
+ * image builds its row in LDS and writes all T0 entries.  A class id outside [0, T0) is skipped and a
+ * duplicated id keeps one of its positions (both are caller bugs; nothing is written out of bounds). */
+int catseg_class_inverse(const int32_t* classes, int64_t B, int k, int T0, int32_t* inv, void* stream);
+/* catseg_class_rows_reduce — the backward of gathering rows per image (model.py:698 torch.gather of the
+ * normalized text; :712-715 the text guidance taken from the gathered rows):
+ * out[t*ld_out + c] = beta * out[..] + sum_b d[(b*k + inv[b][t])*ld_d + c] over the images with
+ * inv[b][t] >= 0, in ascending b by one thread per element; rows no image selected are 0 (beta 0) or left
+ * as they are (beta 1).  d [B*k][cols], out [T0][cols]. */
+int catseg_class_rows_reduce(const float* d, int64_t ld_d, const int32_t* inv, int64_t B, int k, int T0,
+                             int64_t cols, float* out, int64_t ld_out, int beta, void* stream);
+/* catseg_class_planes_gather — out[b][j][p] = in[b][classes[b][j]][p], p < P: the k selected planes of the
+ * cost volume (model.py:702 — the einsum on the gathered text equals the selected planes of corr), and the
+ * backward of the final scatter (model.py:723).  Plane t of image b of `in` at b*in_b_stride +
+ * t*in_t_stride (T0 planes), of `out` at b*out_b_stride + j*out_t_stride (k planes); pixels contiguous.
+ * A class id outside [0, T0) gives a zero plane. */
+int catseg_class_planes_gather(const float* in, int64_t in_t_stride, int64_t in_b_stride, const int32_t* classes,
+                               int64_t B, int k, int T0, int64_t P, float* out, int64_t out_t_stride,
+                               int64_t out_b_stride, void* stream);
+/* catseg_class_planes_scatter — out[b][t][p] = inv[b][t] >= 0 ? in[b][inv[b][t]][p] : fill: torch.full(-100.)
+ * and scatter_ (model.py:722-723) in one pass over the output.  `in` holds k planes per image, `out` T0. */
+int catseg_class_planes_scatter(const float* in, int64_t in_t_stride, int64_t in_b_stride, const int32_t* inv,
+                                int64_t B, int k, int T0, int64_t P, float fill, float* out, int64_t out_t_stride,
+                                int64_t out_b_stride, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Attention backward
  * ------------------------------------------------------------------------- */
 /* catseg_window_attention_backward — WindowAttention backward (model.py:86-114, shift / -100 region mask

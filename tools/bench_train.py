@@ -6,7 +6,8 @@ CATSeg training forward (fp32 CLIP with CLIP_FINETUNE "attention" by default -- 
 -> backward through the HIP kernels -> AdamW with full-model clipping (train_net.py:228-253),
 on the reference training config (configs/vitb_384.yaml: ViT-B/16 @384, COCO-Stuff's 171 classes,
 POOLING [2,2], IMS_PER_BATCH 4, BASE_LR 2e-4, CLIP_GRADIENTS full_model 0.01), synthetic images and
-labels, random-init weights.  Prints one JSON line; --profile adds the per-kernel HIP-event times of one
+labels, random-init weights.  --classes N takes the first N ade847 prompts; N > 256 (pad_len) runs the
+per-image top-k class selection of model.py:691-725 (cat_seg.training).  Prints one JSON line; --profile adds the per-kernel HIP-event times of one
 step (ops.PROFILE).
 """
 import argparse
