@@ -316,6 +316,8 @@ _SIGS = {
     "catseg_class_rows_reduce": [vp, i64, vp, i64, i32, i32, i64, vp, i64, i32, vp],
     "catseg_class_planes_gather": [vp, i64, i64, vp, i64, i32, i32, i64, vp, i64, i64, vp],
     "catseg_class_planes_scatter": [vp, i64, i64, vp, i64, i32, i32, i64, f32, vp, i64, i64, vp],
+    "catseg_train_crop_select": [vp, vp, vp, vp, i32, i32, i32, i32, C.c_double, vp, vp, vp],
+    "catseg_train_augment": [vp, vp, vp, vp, i32, i32, i64, vp, vp, vp],
     "catseg_abi_version": [],
     "catseg_last_error": [],
 }

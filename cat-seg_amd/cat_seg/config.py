@@ -212,4 +212,8 @@ def add_cat_seg_config(cfg):
     # to the tile's extent, averaged with the tiles' merge); catseg_tiled_blend
     cfg.MODEL.CATSEG_HIP.TILED.WINDOW = "uniform"
     cfg.MODEL.CATSEG_HIP.TILED.GLOBAL = False
+    # build_train_loader: "host" = workers run MaskFormerSemanticDatasetMapper (PIL / numpy) | "device" =
+    # workers only decode and the batch is resized, cropped, colour-augmented, flipped and padded by one fused
+    # kernel (catseg_train_augment), byte for byte the host composition of the same draws
+    cfg.MODEL.CATSEG_HIP.TRAIN_INPUT = "host"
     return cfg

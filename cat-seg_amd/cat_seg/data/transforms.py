@@ -18,7 +18,7 @@ uint8 images are resized with PIL (bilinear; nearest for labels), others with to
 from __future__ import annotations
 
 import random
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -190,6 +190,20 @@ def _hsv_to_rgb_u8(hsv):
     return np.clip(np.round(rgb + m[..., None]), 0, 255).astype(np.uint8)
 
 
+class ColorParams(NamedTuple):
+    """One draw of ColorAugSSD: brightness first, then order 1 = contrast, saturation, hue, order 0 =
+    saturation, hue, contrast; each operation runs only with its flag set."""
+    brightness: bool = False
+    beta: float = 0.0
+    order: int = 1
+    contrast: bool = False
+    contrast_alpha: float = 1.0
+    saturation: bool = False
+    saturation_alpha: float = 1.0
+    hue: bool = False
+    hue_delta: int = 0
+
+
 class ColorAugSSD(Transform):
     """point_rend ColorAugSSDTransform: random brightness (+-32), then contrast [0.5, 1.5] and
     saturation [0.5, 1.5] / hue (+-18 on the 180-step wheel) in one of two orders.  The
@@ -214,6 +228,60 @@ class ColorAugSSD(Transform):
         order = (self._contrast, self._saturation, self._hue) if random.randrange(2) else \
             (self._saturation, self._hue, self._contrast)
         for f in order:
+            img = f(img)
+        return img
+
+    def draw(self, rnd=random) -> "ColorParams":
+        """The random draws of one `apply_image` call, from `rnd` (the `random` module or anything with its
+        randrange / uniform / randint) in exactly the order `apply_image` consumes them: after
+        `random.seed(s)`, `apply_image(img)` equals `apply_params(img, draw())` after the same seed."""
+        bright = bool(rnd.randrange(2))
+        beta = rnd.uniform(-self.bd, self.bd) if bright else 0.0
+        order = int(rnd.randrange(2))
+        contrast, c_alpha, sat, s_alpha, hue, delta = False, 1.0, False, 1.0, False, 0
+
+        def _c():
+            nonlocal contrast, c_alpha
+            contrast = bool(rnd.randrange(2))
+            c_alpha = rnd.uniform(self.cl, self.ch) if contrast else 1.0
+
+        def _s():
+            nonlocal sat, s_alpha
+            sat = bool(rnd.randrange(2))
+            s_alpha = rnd.uniform(self.sl, self.sh) if sat else 1.0
+
+        def _h():
+            nonlocal hue, delta
+            hue = bool(rnd.randrange(2))
+            delta = int(rnd.randint(-self.hd, self.hd)) if hue else 0
+
+        for f in ((_c, _s, _h) if order else (_s, _h, _c)):
+            f()
+        return ColorParams(bright, float(beta), order, contrast, float(c_alpha), sat, float(s_alpha), hue, delta)
+
+    def apply_params(self, img, p: "ColorParams"):
+        """`apply_image` with its draws pinned to the record `p` (no randomness consumed)."""
+        if p.brightness:
+            img = self._convert(img, beta=p.beta)
+
+        def _c(x):
+            return self._convert(x, alpha=p.contrast_alpha) if p.contrast else x
+
+        def _s(x):
+            if not p.saturation:
+                return x
+            hsv = _rgb_to_hsv_u8(x)
+            hsv[..., 1] = self._convert(hsv[..., 1], alpha=p.saturation_alpha)
+            return _hsv_to_rgb_u8(hsv)
+
+        def _h(x):
+            if not p.hue:
+                return x
+            hsv = _rgb_to_hsv_u8(x)
+            hsv[..., 0] = (hsv[..., 0].astype(np.int32) + p.hue_delta) % 180
+            return _hsv_to_rgb_u8(hsv)
+
+        for f in ((_c, _s, _h) if p.order else (_s, _h, _c)):
             img = f(img)
         return img
 

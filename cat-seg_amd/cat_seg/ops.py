@@ -951,3 +951,46 @@ def label_runs(labels, *, clamp_pred=-1):
     run_start = torch.empty(R, dtype=torch.int32, device=labels.device)
     run_label = torch.empty(R, dtype=torch.int32, device=labels.device)
     return label_runs_write(labels, ws, run_start, run_label, clamp_pred=clamp_pred)
+
+
+TRAIN_INPUT_MAX_LABELS = 4096
+
+
+def _train_input_args(src, meta, B, desc_words=32):
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.data_ptr() % 16 == 0
+    assert meta.is_cuda and meta.dtype == torch.int32 and meta.is_contiguous() and meta.data_ptr() % 8 == 0
+    assert B > 0 and meta.numel() >= B * desc_words
+
+
+def train_crop_select(src, meta, cand_off, B, n_cand, n_labels, ignore_label, max_area, workspace, crops):
+    """The category-area rule over every image's candidates (catseg_train_crop_select): `src` the packed
+    uint8 pixels, `meta` the packed int32 descriptors (at word 0), candidates (at word cand_off) and tables
+    as cat_seg.data.train_input.plan_batch lays them out; crops (B, 4) int32 receives each image's window.
+    `workspace`: B * (n_cand + 1) int32, zero before its first use."""
+    _train_input_args(src, meta, B)
+    if n_labels > TRAIN_INPUT_MAX_LABELS:
+        raise ValueError(f"train_crop_select: n_labels {n_labels} > {TRAIN_INPUT_MAX_LABELS} (the LDS histogram)")
+    assert crops.is_cuda and crops.dtype == torch.int32 and crops.is_contiguous() and crops.numel() >= 4 * B
+    assert workspace.is_cuda and workspace.dtype == torch.int32 and workspace.numel() >= B * (n_cand + 1)
+    assert cand_off >= 0 and cand_off + B * n_cand * 4 <= meta.numel()
+    with _rec("train_crop_select", 0, 0):
+        call("catseg_train_crop_select", src.data_ptr(), meta.data_ptr(), meta.data_ptr(),
+             meta.data_ptr() + 4 * cand_off, B, n_cand, int(n_labels), int(ignore_label), float(max_area),
+             workspace.data_ptr(), crops.data_ptr(), _stream())
+    return crops
+
+
+def train_augment(src, meta, B, images, targets, ignore_label, crops=None):
+    """Resize + crop + colour + flip + pad of a packed batch in one launch (catseg_train_augment):
+    images (B, 3, S, S) uint8 and targets (B, S, S) int64, contiguous; `crops` the (B, 4) int32 record of
+    train_crop_select when the descriptors select from it."""
+    _train_input_args(src, meta, B)
+    S = images.shape[-1]
+    assert images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and tuple(images.shape) == (B, 3, S, S)
+    assert targets.is_cuda and targets.dtype == torch.int64 and targets.is_contiguous() and tuple(targets.shape) == (B, S, S)
+    assert crops is None or (crops.is_cuda and crops.dtype == torch.int32 and crops.is_contiguous()
+                             and crops.numel() >= 4 * B)
+    with _rec("train_augment", 0, B * S * S * 11):
+        call("catseg_train_augment", src.data_ptr(), meta.data_ptr(), meta.data_ptr(), _p(crops), B, S,
+             int(ignore_label), images.data_ptr(), targets.data_ptr(), _stream())
+    return images, targets

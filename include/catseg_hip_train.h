@@ -338,6 +338,56 @@ int catseg_adamw_step(const CatsegAdamWTensor* tensors, const int64_t* chunk_tab
                       float beta2, float eps, float max_grad_norm, float* norm_out, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Training input: the reference's training mapper
+ * (cat_seg/data/dataset_mappers/mask_former_semantic_dataset_mapper.py:62-147: ResizeShortestEdge,
+ * RandomCrop_CategoryAreaConstraint, ColorAugSSDTransform, RandomFlip, pad to SIZE_DIVISIBILITY) on
+ * decoded uint8 images, per batch, with the random parameters drawn on the host
+ * (cat_seg.data.train_input.draw_train_params).  Byte-exact against the host composition
+ * (cat_seg.data.train_input.reference_apply): integer resampling as PIL's, float32 colour math without
+ * contraction.  Integers only in every count: deterministic.
+ * ------------------------------------------------------------------------- */
+/* One image of the batch; an array of these lives in DEVICE memory.  `src` holds the image as HWC
+ * uint8 at byte img_off and its label plane (HW, lab_bytes = 1: uint8, 4: int32, lab_off % 4 == 0) at
+ * byte lab_off.  Offsets into `tables` are in int32 words: per axis the bounds [n][2] = (first source
+ * index, tap count) and the coefficients [n][k] (fixed point, 22 fraction bits; an axis whose size does
+ * not change has the identity table, one tap of 1 << 22), and the nearest source index [n] of the label
+ * resize.  The crop (y0, x0, ch, cw) in resized coordinates is crop[] or, with crop_sel >= 0, the record
+ * crops[crop_sel] that catseg_train_crop_select wrote.  Colour record: ColorAugSSDTransform's draws
+ * (brightness first; order 1 = contrast, saturation, hue; 0 = saturation, hue, contrast). */
+typedef struct {
+  int64_t img_off, lab_off;
+  int32_t h, w, nh, nw;
+  int32_t xb_off, xk_off, kx, yb_off, yk_off, ky, nx_off, ny_off;
+  int32_t crop[4]; int32_t crop_sel;
+  int32_t flip, lab_bytes;
+  int32_t bright, order, contrast, sat, hue, hue_delta;
+  float beta, c_alpha, s_alpha;
+} CatsegTrainImageDesc;                                                     /* 128 bytes */
+
+/* catseg_train_crop_select — the candidate rule of RandomCrop_CategoryAreaConstraint
+ * (detectron2 augmentation_impl.py RandomCrop_CategoryAreaConstraint.get_transform, reached from
+ * mask_former_semantic_dataset_mapper.py:75-83,117): of image b's n_cand candidate windows
+ * cands[b][c] = (y0, x0, ch, cw) in the nearest-resized label map (read through the index tables, never
+ * materialised) the first in which more than one label other than ignore_label occurs and
+ * (double)max_count < (double)sum * max_area, else the last; written to crops[b].  Labels outside
+ * [0, n_labels) other than ignore_label are not counted; n_labels <= 4096.  One workgroup per (image,
+ * candidate); workspace: B * (n_cand + 1) int32 (flags [B][n_cand], then one counter per image), zero
+ * before the first launch of a given (B, n_cand); the kernel leaves the counters zero again. */
+int catseg_train_crop_select(const uint8_t* src, const int32_t* tables, const CatsegTrainImageDesc* descs,
+                             const int32_t* cands, int B, int n_cand, int n_labels, int ignore_label,
+                             double max_area, int32_t* workspace, int32_t* crops, void* stream);
+
+/* catseg_train_augment — mask_former_semantic_dataset_mapper.py:113-147 for the whole batch in one launch:
+ * images (B, 3, S, S) uint8 and targets (B, S, S) int64, each output pixel computed backwards from the
+ * padded canvas: outside the crop 128 / ignore_label; inside, the flip undone, the crop origin added,
+ * the two-pass integer resample (horizontal result rounded to uint8 first) of the source pixels that
+ * pixel needs, the colour operations of the record, the label through the nearest tables.  No atomics;
+ * every output byte is written exactly once. */
+int catseg_train_augment(const uint8_t* src, const int32_t* tables, const CatsegTrainImageDesc* descs,
+                         const int32_t* crops, int B, int S, int64_t ignore_label, uint8_t* images,
+                         int64_t* targets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
