@@ -13,6 +13,8 @@ this boundary returns one result per input image by default
 (MODEL.CATSEG_HIP.RETURN_ALL_IMAGES; set False for the reference's exact behaviour).
 With MODEL.CATSEG_HIP.TILED.ENABLED an image of any size is segmented at its own resolution: cut into
 tiles, each through the network as an image of its own, merged on the device (engine.forward_tiled).
+With MODEL.CATSEG_HIP.REGIONS.ENABLED (OUTPUT "labels") every returned label map is sieved (MIN_AREA) and
+described by "sem_seg_regions" + "regions_info" on the device (CATSeg.add_regions; ops.label_regions).
 
 Everything between the input copy and the returned tensors runs in the HIP kernels of
 libcatseg_hip.so through `CatSegEngine`; there is no CPU or PyTorch-op fallback.
@@ -72,10 +74,21 @@ class CATSeg(nn.Module):
                  dtype: str = "bf16", return_all_images: bool = True, synthetic_seed: int = 0,
                  vit_fp8: bool = False, graph: bool = True, output: str = "probs", tiled: bool = False,
                  tiled_tile: int = 384, tiled_stride: int = 256, tiled_batch: int = 8, tta_merge: str = "host",
-                 tiled_window: str = "uniform", tiled_global: bool = False):
+                 tiled_window: str = "uniform", tiled_global: bool = False, regions: bool = False,
+                 regions_connectivity: int = 8, regions_min_area: int = 0):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
+        # connected regions / sieve of the returned label maps (MODEL.CATSEG_HIP.REGIONS; ops.label_regions)
+        self.regions = bool(regions)
+        self.regions_connectivity, self.regions_min_area = int(regions_connectivity), int(regions_min_area)
+        if self.regions and output != "labels":
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.REGIONS post-processes the label map of "
+                             f"MODEL.CATSEG_HIP.OUTPUT 'labels', not {output!r}")
+        if self.regions_connectivity not in (4, 8):
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.REGIONS.CONNECTIVITY must be 4 or 8, got {regions_connectivity!r}")
+        if self.regions_min_area < 0:
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.REGIONS.MIN_AREA must be >= 0, got {regions_min_area!r}")
         # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
         self.tiled = bool(tiled)
         self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
@@ -134,6 +147,7 @@ class CATSeg(nn.Module):
     def from_config(cls, cfg):
         hip = cfg.MODEL.get("CATSEG_HIP", {}) if hasattr(cfg.MODEL, "get") else {}
         tiled = (hip.get("TILED", None) if hip else None) or {}
+        regions = (hip.get("REGIONS", None) if hip else None) or {}
         return {
             "backbone": None,
             "sem_seg_head": build_sem_seg_head(cfg, None),
@@ -162,6 +176,9 @@ class CATSeg(nn.Module):
             "tiled_window": str(tiled.get("WINDOW", "uniform")),
             "tiled_global": bool(tiled.get("GLOBAL", False)),
             "tta_merge": str(hip.get("TTA_MERGE", "host")) if hip else "host",
+            "regions": bool(regions.get("ENABLED", False)),
+            "regions_connectivity": int(regions.get("CONNECTIVITY", 8)),
+            "regions_min_area": int(regions.get("MIN_AREA", 0)),
         }
 
     # ------------------------------------------------------------------ parameters
@@ -270,10 +287,28 @@ class CATSeg(nn.Module):
         ops.postprocess_argmax(logits, labels, score, crop=crop)
         return [{"sem_seg_labels": labels[i], "sem_seg_score": score[i]} for i in range(n)]
 
+    def add_regions(self, result: dict) -> dict:
+        """MODEL.CATSEG_HIP.REGIONS: one image's {"sem_seg_labels", "sem_seg_score"} turned into objects, after
+        the graph replay or the merge and outside any captured graph (the table's size depends on the data: one
+        4-byte read of R).  MIN_AREA > 1 replaces "sem_seg_labels" by its sieve ("sem_seg_score" stays as it is);
+        "sem_seg_regions" (the region numbers) and "regions_info" (label, area, bbox, first, score = the mean
+        of "sem_seg_score" over the region) describe the returned map.  A no-op with REGIONS.ENABLED False."""
+        if not self.regions:
+            return result
+        labels, conn = result["sem_seg_labels"], self.regions_connectivity
+        if self.regions_min_area > 1:
+            labels = ops.sieve_labels(labels, self.regions_min_area, connectivity=conn)
+        ids, table = ops.label_regions(labels, connectivity=conn, score=result["sem_seg_score"])
+        table.pop("score_q16")
+        return {**result, "sem_seg_labels": labels, "sem_seg_regions": ids, "regions_info": table}
+
     def _forward_traced(self, batched_inputs: List[dict]):
         """The eval forward as dynamo traces it (torch.compile): the canvas staging in torch ops, the
         network as the one registered operator catseg::head_logits (custom_ops), the resize through
         catseg::postprocess; same kernels and results as the eager branch below."""
+        if self.regions:
+            raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.REGIONS cannot be traced by torch.compile: the "
+                               "region table's size depends on the data; call it eagerly")
         handle = self._op_handle
         n_classes, res = custom_ops.head_meta(handle)
         images = [x["image"] for x in batched_inputs]
@@ -390,14 +425,16 @@ class CATSeg(nn.Module):
         if n > 1 and len(set(outs)) == 1 and len(set(sizes[:n])) == 1:
             # one launch for the whole batch (the engine leg's form); each result is a view of it
             if self.output == "labels":
-                return self._labels(logits[:n], outs[0], (min(h_l, sizes[0][0]), min(w_l, sizes[0][1])))
+                return [self.add_regions(r) for r in
+                        self._labels(logits[:n], outs[0], (min(h_l, sizes[0][0]), min(w_l, sizes[0][1])))]
             out = torch.empty(n, logits.shape[1], outs[0][0], outs[0][1], device=dev)
             ops.postprocess(logits[:n], out, crop=(min(h_l, sizes[0][0]), min(w_l, sizes[0][1])))
             return [{"sem_seg": out[i]} for i in range(n)]
         results = []
         for i in range(n):
             if self.output == "labels":
-                results += self._labels(logits[i:i + 1], outs[i], (min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))
+                results += [self.add_regions(r) for r in
+                            self._labels(logits[i:i + 1], outs[i], (min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))]
                 continue
             out = torch.empty(1, logits.shape[1], outs[i][0], outs[i][1], device=dev)
             ops.postprocess(logits[i:i + 1], out, crop=(min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))
@@ -456,7 +493,8 @@ class CATSeg(nn.Module):
                 h = int(batched_inputs[i].get("height", ih))
                 w = int(batched_inputs[i].get("width", iw))
                 if self.output == "labels":
-                    results += self._labels(logits[i:i + 1], (h, w), (min(h_l, ih), min(w_l, iw)))
+                    results += [self.add_regions(r) for r in
+                                self._labels(logits[i:i + 1], (h, w), (min(h_l, ih), min(w_l, iw)))]
                     continue
                 out = torch.empty(1, logits.shape[1], h, w, device=eng.device)
                 ops.postprocess(logits[i:i + 1], out, crop=(min(h_l, ih), min(w_l, iw)))
@@ -488,7 +526,7 @@ class CATSeg(nn.Module):
                                         stride=self.tiled_stride, batch=self.tiled_batch,
                                         window=self.tiled_window, global_view=self.tiled_global)
                 if self.output == "labels":
-                    results.append({"sem_seg_labels": out[0], "sem_seg_score": out[1]})
+                    results.append(self.add_regions({"sem_seg_labels": out[0], "sem_seg_score": out[1]}))
                 else:
                     results.append({"sem_seg": out})
             return results
@@ -547,7 +585,7 @@ class CATSeg(nn.Module):
             res = eng.SLIDE_OUT
             out_hw = [(int(x.get("height", res)), int(x.get("width", res))) for x in inputs]
             if self.output == "labels":
-                return [{"sem_seg_labels": lab, "sem_seg_score": sc}
+                return [self.add_regions({"sem_seg_labels": lab, "sem_seg_score": sc})
                         for lab, sc in eng.forward_sliding(raw, sizes_dev, out_hw, labels=True)]
             return [{"sem_seg": o} for o in eng.forward_sliding(raw, sizes_dev, out_hw)]
 

@@ -216,4 +216,12 @@ def add_cat_seg_config(cfg):
     # workers only decode and the batch is resized, cropped, colour-augmented, flipped and padded by one fused
     # kernel (catseg_train_augment), byte for byte the host composition of the same draws
     cfg.MODEL.CATSEG_HIP.TRAIN_INPUT = "host"
+    # OUTPUT "labels" only: every returned label map is turned into objects on the device (ops.label_regions /
+    # ops.sieve_labels): MIN_AREA > 1 replaces "sem_seg_labels" by its sieve (regions smaller than MIN_AREA pixels
+    # take the label of their largest large neighbour), then "sem_seg_regions" ((H, W) int32 region numbers) and
+    # "regions_info" (label, area, bbox, first, score per region) describe the returned map.  CONNECTIVITY 4 | 8
+    cfg.MODEL.CATSEG_HIP.REGIONS = C()
+    cfg.MODEL.CATSEG_HIP.REGIONS.ENABLED = False
+    cfg.MODEL.CATSEG_HIP.REGIONS.CONNECTIVITY = 8
+    cfg.MODEL.CATSEG_HIP.REGIONS.MIN_AREA = 0
     return cfg

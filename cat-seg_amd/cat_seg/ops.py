@@ -953,6 +953,115 @@ def label_runs(labels, *, clamp_pred=-1):
     return label_runs_write(labels, ws, run_start, run_label, clamp_pred=clamp_pred)
 
 
+def _regions_args(labels, connectivity, what):
+    H, W, ld = _label_map_args(labels, what)
+    if connectivity not in (4, 8):
+        raise ValueError(f"{what}: connectivity must be 4 or 8, got {connectivity!r}")
+    return H, W, ld
+
+
+def _regions_workspace(H, W, sieve, device, what):
+    nbytes = L.load().catseg_label_regions_workspace(H, W, int(sieve))
+    if nbytes <= 0:
+        raise ValueError(f"{what}: a {H} x {W} map needs H * W < 2^31")
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device), nbytes
+
+
+def label_regions_count(labels, *, connectivity=8, clamp_pred=-1):
+    """Labelling + scan half of `label_regions` (catseg_label_regions_count): returns the int32 workspace
+    tensor, whose element 0 is the number of regions R (still on the device)."""
+    H, W, ld = _regions_args(labels, connectivity, "label_regions")
+    ws, nbytes = _regions_workspace(H, W, False, labels.device, "label_regions")
+    with _rec("label_regions_count", 0, 4 * H * W + nbytes):
+        call("catseg_label_regions_count", labels.data_ptr(), H, W, ld, int(clamp_pred), int(connectivity),
+             ws.data_ptr(), nbytes, _stream())
+    return ws
+
+
+def label_regions_write(labels, ws, region_ids, table, *, clamp_pred=-1, score=None):
+    """Write half of `label_regions` (catseg_label_regions_write): fills `region_ids` ((H, W) int32, rows may
+    be strided) and the first min(R, capacity) rows of `table`, a dict of device tensors "label", "area", "first"
+    (capacity,) int32, "bbox" (capacity, 4) int32 and, with `score` ((H, W) fp32), "score_q16" (capacity,) int64.
+    Nothing is stored at a row >= capacity.  No host synchronisation."""
+    H, W, ld = _label_map_args(labels, "label_regions")
+    if _label_map_args(region_ids, "label_regions (region_ids)")[:2] != (H, W):
+        raise ValueError("label_regions: region_ids must have the map's shape")
+    ld_ids = region_ids.stride(0) if H > 1 else W
+    assert ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous()
+    cols = [table[k] for k in ("label", "area", "bbox", "first")]
+    cap = cols[0].numel()
+    for k, t in zip(("label", "area", "bbox", "first"), cols):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous(), k
+        assert tuple(t.shape) == ((cap, 4) if k == "bbox" else (cap,)), k
+    sp = ld_s = q16p = 0
+    if score is not None:
+        if not (score.is_cuda and score.dtype == torch.float32 and tuple(score.shape) == (H, W)
+                and (W == 1 or score.stride(1) == 1)):
+            raise ValueError("label_regions: score must be an (H, W) fp32 CUDA tensor with contiguous rows")
+        ld_s = score.stride(0) if H > 1 else W
+        q16 = table["score_q16"]
+        assert q16.is_cuda and q16.dtype == torch.int64 and q16.is_contiguous() and tuple(q16.shape) == (cap,)
+        sp, q16p = score.data_ptr(), q16.data_ptr()
+    with _rec("label_regions_write", 0, 12 * H * W + 36 * cap):
+        call("catseg_label_regions_write", labels.data_ptr(), H, W, ld, int(clamp_pred), sp or None, ld_s, ws.data_ptr(),
+             ws.numel() * 4, region_ids.data_ptr(), ld_ids, *(t.data_ptr() or None for t in cols), q16p or None, cap,
+             _stream())
+    return region_ids, table
+
+
+def label_regions(labels, *, connectivity=8, clamp_pred=-1, score=None):
+    """The connected regions of a label map (catseg_label_regions_count / _write): maximal
+    sets of pixels of equal label (labels >= clamp_pred folded to clamp_pred; clamp_pred < 0: no fold) connected
+    under `connectivity` 4 or 8, numbered 0 .. R-1 in row-major order of their first pixel.  labels: 2-D int32
+    CUDA tensor, possibly a row-strided view.  Returns (region_ids, table): region_ids (H, W) int32, table a dict
+    of device tensors of exactly R rows: "label" (folded), "area", "first" (y * W + x of the first pixel) int32,
+    "bbox" (R, 4) int32 [x0, y0, x1, y1] with x1 / y1 exclusive and, with `score` ((H, W) fp32), "score_q16" int64,
+    the sum over the region of rint(score * 65536) (an integer sum: the same bits in any order) and "score" fp32,
+    the mean derived from it.
+
+    Runs labelling + scan, reads R from the device (one synchronising 4-byte copy), allocates exactly R and runs
+    the write pass.  Not registered as a torch.ops.catseg.* custom op: the output size depends on the data."""
+    ws = label_regions_count(labels, connectivity=connectivity, clamp_pred=clamp_pred)
+    R = int(ws[0].item())
+    dev = labels.device
+    table = {"label": torch.empty(R, dtype=torch.int32, device=dev), "area": torch.empty(R, dtype=torch.int32, device=dev),
+             "bbox": torch.empty(R, 4, dtype=torch.int32, device=dev), "first": torch.empty(R, dtype=torch.int32, device=dev)}
+    if score is not None:
+        table["score_q16"] = torch.empty(R, dtype=torch.int64, device=dev)
+    region_ids = torch.empty(labels.shape, dtype=torch.int32, device=dev)
+    label_regions_write(labels, ws, region_ids, table, clamp_pred=clamp_pred, score=score)
+    if score is not None:
+        table["score"] = region_mean_score(table["score_q16"], table["area"])
+    return region_ids, table
+
+
+def region_mean_score(score_q16, area):
+    """The mean score of every region from the table's fixed-point sum: score_q16 / 65536 / area in fp64, then fp32."""
+    return (score_q16.double() / 65536.0 / area.double()).float()
+
+
+def sieve_labels(labels, min_area, *, connectivity=8, clamp_pred=-1, out=None):
+    """The minimum-mapping-unit sieve of a label map (catseg_sieve_labels), one pass: with
+    the regions of `labels` (as `label_regions` defines them), every region of area < min_area that touches a
+    region of area >= min_area takes the (folded) label of the touching one with the largest area, ties to the
+    smallest region number; every other pixel keeps its value (min_area 1 copies the map).  labels: 2-D int32
+    CUDA tensor, rows may be strided; out: the same shape (fresh when None), rows may be strided, must not
+    overlap labels.  Returns out.  No host synchronisation."""
+    H, W, ld = _regions_args(labels, connectivity, "sieve_labels")
+    if int(min_area) < 1:
+        raise ValueError(f"sieve_labels: min_area must be >= 1, got {min_area!r}")
+    ws, nbytes = _regions_workspace(H, W, True, labels.device, "sieve_labels")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=labels.device)
+    if _label_map_args(out, "sieve_labels (out)")[:2] != (H, W):
+        raise ValueError("sieve_labels: out must have the map's shape")
+    ld_out = out.stride(0) if H > 1 else W
+    with _rec("sieve_labels", 0, 8 * H * W + nbytes):
+        call("catseg_sieve_labels", labels.data_ptr(), H, W, ld, int(clamp_pred), int(connectivity), int(min_area),
+             out.data_ptr(), ld_out, ws.data_ptr(), nbytes, _stream())
+    return out
+
+
 TRAIN_INPUT_MAX_LABELS = 4096
 
 

@@ -16,8 +16,8 @@
 //           into LDS; then a wave takes whole columns, one lane per row, and the start flags of the 64 rows
 //           of one column -- segment (x, chunk = y / 64) -- are one __ballot mask: its popcount is the
 //           segment's count.  Segments numbered x * nchunks + chunk are in column-major order.
-//   scan    exclusive scan of the segment counts (block sums, one block over the block sums, block scans):
-//           every segment's write offset, and the total R.
+//   scan    exclusive scan of the segment counts (scan_i32.h: block sums, one block over the block sums,
+//           block scans): every segment's write offset, and the total R.
 //   write   the count pass again; a start stores (p, label) at offset + the number of set lower lanes.
 //           Nothing is stored at an index >= capacity, whatever the map holds.
 //
@@ -26,13 +26,12 @@
 // the load are consecutive addresses.
 #include "common.h"
 #include "capi.h"
+#include "scan_i32.h"
 
 namespace {
 
 constexpr int LR_TILE = 64;                       // rows and columns of a tile; rows = lanes of a wave
 constexpr int LR_PITCH = LR_TILE + 1;
-constexpr int LR_PER_THREAD = 8;
-constexpr int LR_SCAN = 256 * LR_PER_THREAD;      // counts per block of the scan passes
 constexpr int LR_HEAD = 4;                        // workspace header (ints): [0] = R; keeps the offsets 16-byte aligned
 
 DEV int lr_fold(int l, int clamp) { return (clamp >= 0 && l >= clamp) ? clamp : l; }
@@ -92,82 +91,6 @@ __global__ __launch_bounds__(256) void label_runs_kernel(const int32_t* __restri
   }
 }
 
-// exclusive scan of one value per thread over the 256 threads of a block; total = the block's sum
-DEV int lr_block_exscan(int v, int* sh, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) sh[wv] = inc;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int s = sh[i];
-    base += i < wv ? s : 0;
-    total += s;
-  }
-  __syncthreads();                                 // sh may be written again
-  return base + inc - v;
-}
-
-// bsum[b] = the sum of counts [b * LR_SCAN, (b + 1) * LR_SCAN)
-__global__ __launch_bounds__(256) void lr_block_sums_kernel(const int32_t* __restrict__ counts, int64_t n,
-                                                            int32_t* __restrict__ bsum) {
-  __shared__ int sh[4];
-  const int64_t base = (int64_t)blockIdx.x * LR_SCAN;
-  int v = 0;
-#pragma unroll
-  for (int j = 0; j < LR_PER_THREAD; ++j) {
-    const int64_t i = base + j * 256 + threadIdx.x;
-    v += i < n ? counts[i] : 0;
-  }
-  int total;
-  lr_block_exscan(v, sh, total);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one block: bsum -> its exclusive scan, in strips of 256 with a carry; *total = the sum of all of it
-__global__ __launch_bounds__(256) void lr_scan_top_kernel(int32_t* __restrict__ bsum, int64_t nb,
-                                                          int32_t* __restrict__ total_out) {
-  __shared__ int sh[4];
-  int carry = 0;
-  for (int64_t base = 0; base < nb; base += 256) {
-    const int64_t i = base + threadIdx.x;
-    const int v = i < nb ? bsum[i] : 0;
-    int total;
-    const int ex = lr_block_exscan(v, sh, total);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) total_out[0] = carry;
-}
-
-// counts -> offsets in place: a thread owns LR_PER_THREAD consecutive counts of its block's range
-__global__ __launch_bounds__(256) void lr_scan_apply_kernel(int32_t* __restrict__ counts, int64_t n,
-                                                            const int32_t* __restrict__ bsum) {
-  __shared__ int sh[4];
-  const int64_t first = (int64_t)blockIdx.x * LR_SCAN + (int64_t)threadIdx.x * LR_PER_THREAD;
-  int c[LR_PER_THREAD];
-  int v = 0;
-#pragma unroll
-  for (int j = 0; j < LR_PER_THREAD; ++j) {
-    c[j] = first + j < n ? counts[first + j] : 0;
-    v += c[j];
-  }
-  int total;
-  int run = bsum[blockIdx.x] + lr_block_exscan(v, sh, total);
-#pragma unroll
-  for (int j = 0; j < LR_PER_THREAD; ++j) {
-    if (first + j < n) counts[first + j] = run;
-    run += c[j];
-  }
-}
-
 struct LrShape {
   int64_t nchunks, nseg, nb, tiles;
 };
@@ -216,9 +139,7 @@ extern "C" int catseg_label_runs_count(const int32_t* labels, int64_t H, int64_t
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(label_runs_kernel<false>, dim3((unsigned)sh.tiles), dim3(256), 0, st, labels, (int)H, (int)W, ld,
                      clamp_pred, (int)sh.nchunks, seg, (int32_t*)nullptr, (int32_t*)nullptr, (int64_t)0);
-  hipLaunchKernelGGL(lr_block_sums_kernel, dim3((unsigned)sh.nb), dim3(256), 0, st, seg, sh.nseg, bsum);
-  hipLaunchKernelGGL(lr_scan_top_kernel, dim3(1), dim3(256), 0, st, bsum, sh.nb, ws);
-  hipLaunchKernelGGL(lr_scan_apply_kernel, dim3((unsigned)sh.nb), dim3(256), 0, st, seg, sh.nseg, bsum);
+  lr_scan_launch(seg, sh.nseg, bsum, ws, st);
   return catseg_launch_status("label_runs_count");
 }
 

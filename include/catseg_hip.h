@@ -620,6 +620,48 @@ int catseg_label_runs_write(const int32_t* labels, int64_t H, int64_t W, int64_t
                             const void* workspace, int64_t workspace_bytes, int32_t* run_start,
                             int32_t* run_label, int64_t capacity, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * catseg_label_regions_* / catseg_sieve_labels — the connected regions of an int32 label map,
+ * their table, and the minimum-mapping-unit sieve, on the device.  No counterpart in the
+ * reference (its users run scipy.ndimage.label per class on a host copy); the contract is
+ * DESIGN.md section 4, "Connected regions and the sieve".
+ *   labels [H][W] int32, row stride ld >= W elements; any int32 value is a label, compared for
+ *   equality after fold(l) = (clamp_pred >= 0 && l >= clamp_pred) ? clamp_pred : l.
+ *   A region is a maximal set of pixels of equal folded label connected under `connectivity`
+ *   4 or 8.  Regions are numbered 0 .. R-1 in row-major order of their first pixel (the minimum
+ *   of p = y * W + x over the region).  Needs H * W < 2^31.  Every result is a function of the
+ *   input alone (no dependence on scheduling).
+ *
+ * catseg_label_regions_workspace  bytes of workspace for an (H, W) map, for _count / _write
+ *     (sieve == 0) or for catseg_sieve_labels (sieve != 0); 0 for a bad shape.
+ * catseg_label_regions_count      labels the map (union-find, three launches) and scans the
+ *     region roots.  Afterwards ((int32_t*)workspace)[0] = R.  workspace: 16-byte aligned
+ *     device memory.  The caller reads R (a device-to-host copy of its own) to size the table.
+ * catseg_label_regions_write      with the workspace _count left for the same map and arguments:
+ *     region_ids [H][W] int32 (row stride ld_ids >= W, the slack never written) and the table,
+ *     rows i < min(R, capacity): label[i] (folded), area[i], bbox[4 i ..] = x0, y0, x1, y1 (x1,
+ *     y1 exclusive), first[i] = p of the first pixel, and, when score ([H][W] fp32, row stride
+ *     ld_score) and score_q16 are given, score_q16[i] = the sum over the region's pixels of
+ *     (int64) rintf(score * 65536.0f).  Integer atomics: the same bits in any order.  Never
+ *     stores at a row >= capacity; leaves the workspace as it is.  capacity 0: ids only.
+ * catseg_sieve_labels             one pass, not iterated: with the regions of the input map, a
+ *     region of area < min_area that touches regions of area >= min_area takes the folded label
+ *     of the one with the largest area (ties: the smallest region number); every other pixel
+ *     keeps its value, so min_area 1 copies the map.  out [H][W] int32 (row stride ld_out >= W,
+ *     the slack never written) must not overlap labels.  No host synchronisation.
+ * ------------------------------------------------------------------------- */
+int64_t catseg_label_regions_workspace(int64_t H, int64_t W, int sieve);
+int catseg_label_regions_count(const int32_t* labels, int64_t H, int64_t W, int64_t ld, int clamp_pred,
+                               int connectivity, void* workspace, int64_t workspace_bytes, void* stream);
+int catseg_label_regions_write(const int32_t* labels, int64_t H, int64_t W, int64_t ld, int clamp_pred,
+                               const float* score, int64_t ld_score, const void* workspace,
+                               int64_t workspace_bytes, int32_t* region_ids, int64_t ld_ids,
+                               int32_t* label, int32_t* area, int32_t* bbox, int32_t* first,
+                               int64_t* score_q16, int64_t capacity, void* stream);
+int catseg_sieve_labels(const int32_t* labels, int64_t H, int64_t W, int64_t ld, int clamp_pred,
+                        int connectivity, int64_t min_area, int32_t* out, int64_t ld_out, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
