@@ -227,6 +227,10 @@ _SIGS = {
     "catseg_label_regions_count": [vp, i64, i64, i64, i32, i32, vp, i64, vp],
     "catseg_label_regions_write": [vp, i64, i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp],
     "catseg_sieve_labels": [vp, i64, i64, i64, i32, i32, i64, vp, i64, vp, i64, vp],
+    "catseg_region_outlines_workspace": [i64, i64, i64],
+    "catseg_region_outlines_count": [vp, i64, i64, i64, i32, vp, i64, vp],
+    "catseg_region_outlines_rank": [vp, i64, i64, i64, i32, vp, i64, i64, vp, i64, vp],
+    "catseg_region_outlines_write": [vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, i64, vp, i64, vp],
     "catseg_rows_gemm": [vp, i64, i64, vp, vp, f32, vp, i64, C.POINTER(RowsEpi), i32, vp],
     "catseg_rows_mlp": [vp, i64, i64, vp, vp, f32, vp, vp, i64, i32, vp, C.POINTER(RowsEpi), i32, vp],
     "catseg_layernorm": [vp, i64, RowMap, i32, vp, i64, i32, vp, vp, i64, i64, f32, vp],

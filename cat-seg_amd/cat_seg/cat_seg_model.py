@@ -14,7 +14,8 @@ this boundary returns one result per input image by default
 With MODEL.CATSEG_HIP.TILED.ENABLED an image of any size is segmented at its own resolution: cut into
 tiles, each through the network as an image of its own, merged on the device (engine.forward_tiled).
 With MODEL.CATSEG_HIP.REGIONS.ENABLED (OUTPUT "labels") every returned label map is sieved (MIN_AREA) and
-described by "sem_seg_regions" + "regions_info" on the device (CATSeg.add_regions; ops.label_regions).
+described by "sem_seg_regions" + "regions_info" on the device (CATSeg.add_regions; ops.label_regions), and with
+REGIONS.OUTLINES by "regions_outlines", the regions' boundaries as polygon rings (ops.region_outlines).
 
 Everything between the input copy and the returned tensors runs in the HIP kernels of
 libcatseg_hip.so through `CatSegEngine`; there is no CPU or PyTorch-op fallback.
@@ -75,7 +76,7 @@ class CATSeg(nn.Module):
                  vit_fp8: bool = False, graph: bool = True, output: str = "probs", tiled: bool = False,
                  tiled_tile: int = 384, tiled_stride: int = 256, tiled_batch: int = 8, tta_merge: str = "host",
                  tiled_window: str = "uniform", tiled_global: bool = False, regions: bool = False,
-                 regions_connectivity: int = 8, regions_min_area: int = 0):
+                 regions_connectivity: int = 8, regions_min_area: int = 0, regions_outlines: bool = False):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
@@ -89,6 +90,11 @@ class CATSeg(nn.Module):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.REGIONS.CONNECTIVITY must be 4 or 8, got {regions_connectivity!r}")
         if self.regions_min_area < 0:
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.REGIONS.MIN_AREA must be >= 0, got {regions_min_area!r}")
+        # the regions' boundaries as polygon rings (MODEL.CATSEG_HIP.REGIONS.OUTLINES; ops.region_outlines)
+        self.regions_outlines = bool(regions_outlines)
+        if self.regions_outlines and not self.regions:
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.REGIONS.OUTLINES traces the regions of "
+                             "MODEL.CATSEG_HIP.REGIONS.ENABLED, which is off")
         # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
         self.tiled = bool(tiled)
         self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
@@ -179,6 +185,7 @@ class CATSeg(nn.Module):
             "regions": bool(regions.get("ENABLED", False)),
             "regions_connectivity": int(regions.get("CONNECTIVITY", 8)),
             "regions_min_area": int(regions.get("MIN_AREA", 0)),
+            "regions_outlines": bool(regions.get("OUTLINES", False)),
         }
 
     # ------------------------------------------------------------------ parameters
@@ -292,7 +299,10 @@ class CATSeg(nn.Module):
         the graph replay or the merge and outside any captured graph (the table's size depends on the data: one
         4-byte read of R).  MIN_AREA > 1 replaces "sem_seg_labels" by its sieve ("sem_seg_score" stays as it is);
         "sem_seg_regions" (the region numbers) and "regions_info" (label, area, bbox, first, score = the mean
-        of "sem_seg_score" over the region) describe the returned map.  A no-op with REGIONS.ENABLED False."""
+        of "sem_seg_score" over the region) describe the returned map.  With REGIONS.OUTLINES, "regions_outlines" =
+        ops.region_outlines of "sem_seg_regions" (two more 4-byte reads: corners, rings): ring_value is a region
+        number, every region has one exterior ring, and they come in region order.  A no-op with REGIONS.ENABLED
+        False."""
         if not self.regions:
             return result
         labels, conn = result["sem_seg_labels"], self.regions_connectivity
@@ -300,7 +310,10 @@ class CATSeg(nn.Module):
             labels = ops.sieve_labels(labels, self.regions_min_area, connectivity=conn)
         ids, table = ops.label_regions(labels, connectivity=conn, score=result["sem_seg_score"])
         table.pop("score_q16")
-        return {**result, "sem_seg_labels": labels, "sem_seg_regions": ids, "regions_info": table}
+        out = {**result, "sem_seg_labels": labels, "sem_seg_regions": ids, "regions_info": table}
+        if self.regions_outlines:
+            out["regions_outlines"] = ops.region_outlines(ids, connectivity=conn)
+        return out
 
     def _forward_traced(self, batched_inputs: List[dict]):
         """The eval forward as dynamo traces it (torch.compile): the canvas staging in torch ops, the

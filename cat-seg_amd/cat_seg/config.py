@@ -224,4 +224,7 @@ def add_cat_seg_config(cfg):
     cfg.MODEL.CATSEG_HIP.REGIONS.ENABLED = False
     cfg.MODEL.CATSEG_HIP.REGIONS.CONNECTIVITY = 8
     cfg.MODEL.CATSEG_HIP.REGIONS.MIN_AREA = 0
+    # REGIONS.ENABLED only: "regions_outlines" = ops.region_outlines of "sem_seg_regions" under CONNECTIVITY, the
+    # regions' boundaries as polygon rings on the device (cat_seg.vectorize turns them into GeoJSON)
+    cfg.MODEL.CATSEG_HIP.REGIONS.OUTLINES = False
     return cfg

@@ -1062,6 +1062,99 @@ def sieve_labels(labels, min_area, *, connectivity=8, clamp_pred=-1, out=None):
     return out
 
 
+def _outlines_args(ids, connectivity, what):
+    H, W, ld = _label_map_args(ids, what)
+    if connectivity not in (4, 8):
+        raise ValueError(f"{what}: connectivity must be 4 or 8, got {connectivity!r}")
+    return H, W, ld
+
+
+def _outlines_workspace(H, W, corners, device, what):
+    nbytes = L.load().catseg_region_outlines_workspace(H, W, int(corners))
+    if nbytes <= 0:
+        raise ValueError(f"{what}: a {H} x {W} map needs H * W < 2^31 and 4 (H + 1) (W + 1) < 2^31" +
+                         (f", and at most 4 (H + 1) (W + 1) corners (got {corners})" if corners >= 0 else ""))
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device), nbytes
+
+
+def region_outlines_count(ids, *, connectivity=8):
+    """Corner count + scan third of `region_outlines` (catseg_region_outlines_count): returns the int32 map
+    workspace, whose element 0 is the number of corners K (still on the device).  No host synchronisation."""
+    H, W, ld = _outlines_args(ids, connectivity, "region_outlines")
+    ws, nbytes = _outlines_workspace(H, W, -1, ids.device, "region_outlines")
+    with _rec("region_outlines_count", 0, 4 * H * W + nbytes):
+        call("catseg_region_outlines_count", ids.data_ptr(), H, W, ld, int(connectivity), ws.data_ptr(), nbytes,
+             _stream())
+    return ws
+
+
+def region_outlines_rank(ids, ws, corners, *, connectivity=8):
+    """Link + ranking third of `region_outlines` (catseg_region_outlines_rank): with the map workspace `ws` of
+    `region_outlines_count` and corners = K read from it, returns the int32 ring workspace, whose element 1 is the
+    number of rings NR (still on the device).  No host synchronisation."""
+    H, W, ld = _outlines_args(ids, connectivity, "region_outlines")
+    corners = int(corners)
+    if corners < 1:
+        raise ValueError(f"region_outlines: corners must be >= 1, got {corners}")
+    assert ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous()
+    rws, nbytes = _outlines_workspace(H, W, corners, ids.device, "region_outlines")
+    with _rec("region_outlines_rank", 0, 4 * H * W + ws.numel() * 4 + nbytes):
+        call("catseg_region_outlines_rank", ids.data_ptr(), H, W, ld, int(connectivity), ws.data_ptr(), ws.numel() * 4,
+             corners, rws.data_ptr(), nbytes, _stream())
+    return rws
+
+
+def region_outlines_write(ids, rws, corners, out):
+    """Write third of `region_outlines` (catseg_region_outlines_write): with the ring workspace `rws` of
+    `region_outlines_rank` for the same corners, fills `out`, a dict of device tensors "ring_offset" (capacity + 1,)
+    int32, "ring_value" (capacity,) int32, "ring_area2" (capacity,) int64 and "vertices" (vertex capacity, 2) int32:
+    rings below min(NR, capacity) and vertices below the vertex capacity; nothing is stored beyond either.  No host
+    synchronisation."""
+    H, W, ld = _label_map_args(ids, "region_outlines")
+    corners = int(corners)
+    assert rws.is_cuda and rws.dtype == torch.int32 and rws.is_contiguous()
+    off, val, a2, vert = (out[k] for k in ("ring_offset", "ring_value", "ring_area2", "vertices"))
+    for k, t, dt in (("ring_offset", off, torch.int32), ("ring_value", val, torch.int32),
+                     ("ring_area2", a2, torch.int64), ("vertices", vert, torch.int32)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise ValueError(f"region_outlines: {k} must be a contiguous {dt} CUDA tensor")
+    cap = val.numel()
+    if off.dim() != 1 or val.dim() != 1 or tuple(off.shape) != (cap + 1,) or tuple(a2.shape) != (cap,):
+        raise ValueError("region_outlines: ring_offset must have one element more than ring_value and ring_area2")
+    if vert.dim() != 2 or vert.shape[1] != 2:
+        raise ValueError(f"region_outlines: vertices must be (capacity, 2), got {tuple(vert.shape)}")
+    with _rec("region_outlines_write", 0, rws.numel() * 4 + 16 * cap + 8 * vert.shape[0]):
+        call("catseg_region_outlines_write", ids.data_ptr(), H, W, ld, rws.data_ptr(), rws.numel() * 4, corners,
+             off.data_ptr(), val.data_ptr() or None, a2.data_ptr() or None, cap, vert.data_ptr() or None,
+             vert.shape[0], _stream())
+    return out
+
+
+def region_outlines(ids, *, connectivity=8):
+    """The outlines of the regions of a map as polygon rings (catseg_region_outlines_*; DESIGN.md section 4,
+    "Region outlines").  ids: 2-D int32 CUDA tensor, possibly a row-strided view; in practice the region numbers of
+    `label_regions` under the same connectivity.  Vertices are pixel corners, x in 0..W, y in 0..H, y down.  A ring
+    keeps its value on its right: an exterior ring runs clockwise on screen and has ring_area2 > 0, a hole has
+    ring_area2 < 0.  At a diagonal pinch a ring turns left under connectivity 8 and right under 4.  Collinear points
+    are dropped; a ring is closed implicitly and starts at its corner of smallest key (y * (W + 1) + x) * 4 + d_in;
+    rings are ordered by that key.  Returns a dict of device tensors, allocated exactly: "ring_offset" (NR + 1,)
+    int32, "ring_value" (NR,) int32, "ring_area2" (NR,) int64 (the shoelace sum, twice the signed area) and
+    "vertices" (K, 2) int32 [x, y]; ring j is vertices[ring_offset[j]:ring_offset[j + 1]].
+
+    Two synchronising 4-byte reads (K, then NR) size the buffers.  Not registered as a torch.ops.catseg.* custom op:
+    the output sizes depend on the data."""
+    ws = region_outlines_count(ids, connectivity=connectivity)
+    K = int(ws[0].item())
+    rws = region_outlines_rank(ids, ws, K, connectivity=connectivity)
+    NR = int(rws[1].item())
+    dev = ids.device
+    out = {"ring_offset": torch.empty(NR + 1, dtype=torch.int32, device=dev),
+           "ring_value": torch.empty(NR, dtype=torch.int32, device=dev),
+           "ring_area2": torch.empty(NR, dtype=torch.int64, device=dev),
+           "vertices": torch.empty(K, 2, dtype=torch.int32, device=dev)}
+    return region_outlines_write(ids, rws, K, out)
+
+
 TRAIN_INPUT_MAX_LABELS = 4096
 
 

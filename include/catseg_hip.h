@@ -662,6 +662,51 @@ int catseg_sieve_labels(const int32_t* labels, int64_t H, int64_t W, int64_t ld,
                         int connectivity, int64_t min_area, int32_t* out, int64_t ld_out, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * catseg_region_outlines_* — the boundaries of the regions of an int32 map (in practice the
+ * region_ids of catseg_label_regions_write) traced into polygon rings, on the device.  No
+ * counterpart in the reference (its users polygonize a host copy); the contract is DESIGN.md
+ * section 4, "Region outlines".
+ *   ids [H][W] int32, row stride ld >= W elements; values are compared for equality, outside
+ *   the map differs from every pixel.  Lattice vertex (x, y), x in 0..W, y in 0..H, y down, is
+ *   the top-left corner of pixel (y, x); directions E=0, S=1, W=2, N=3.  A ring keeps its value
+ *   on its right: exterior rings run clockwise on screen (area2 > 0), holes the other way.  At a
+ *   diagonal pinch a ring turns left under connectivity 8 and right under 4.  A corner is a
+ *   vertex where a ring turns, with key (y * (W + 1) + x) * 4 + d_in; a ring starts at its
+ *   corner of smallest key and rings are ordered by that key.  K = the number of corners, NR =
+ *   the number of rings.  Needs H * W < 2^31 and 4 (H + 1) (W + 1) < 2^31.  Every result is a
+ *   function of the input alone.  Two synchronising reads per map (K, NR) size everything.
+ *
+ * catseg_region_outlines_workspace  corners < 0: bytes of the map workspace of an (H, W) map;
+ *     corners >= 0: bytes of the ring workspace for that many corners; 0 for a bad shape.
+ * catseg_region_outlines_count      counts the corners per 64 lattice vertices, builds the corner
+ *     bitmaps and scans the counts.  Afterwards ((int32_t*)workspace)[0] = K.  workspace: 16-byte
+ *     aligned device memory.  The caller reads K to size the ring workspace.
+ * catseg_region_outlines_rank       with the map workspace _count left for the same map and
+ *     connectivity and corners = K: links every corner to its successor, ranks the rings by
+ *     ceil(log2 corners) rounds of pointer jumping (one launch each) and scans ring starts and
+ *     lengths.  Afterwards ((int32_t*)ring_workspace)[1] = NR.  The caller reads NR to size the
+ *     ring columns.  Leaves the map workspace as it is.
+ * catseg_region_outlines_write      with the ring workspace _rank left for the same map and
+ *     corners: ring_offset[j] for j <= min(NR, ring_capacity) (ring_offset[NR] = K; the buffer has
+ *     ring_capacity + 1 elements), ring_value[j] and ring_area2[j] (the shoelace sum, an int64
+ *     integer sum: the same bits in any order) for j < min(NR, ring_capacity), and vertices
+ *     [2 p], [2 p + 1] = x, y of the corner at position p = ring_offset[ring] + rank for
+ *     p < vertex_capacity (vertices: 8-byte aligned).  Never stores beyond a capacity, whatever
+ *     the map or the workspace holds; leaves the workspace as it is.
+ * ------------------------------------------------------------------------- */
+int64_t catseg_region_outlines_workspace(int64_t H, int64_t W, int64_t corners);
+int catseg_region_outlines_count(const int32_t* ids, int64_t H, int64_t W, int64_t ld, int connectivity,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+int catseg_region_outlines_rank(const int32_t* ids, int64_t H, int64_t W, int64_t ld, int connectivity,
+                                const void* workspace, int64_t workspace_bytes, int64_t corners,
+                                void* ring_workspace, int64_t ring_workspace_bytes, void* stream);
+int catseg_region_outlines_write(const int32_t* ids, int64_t H, int64_t W, int64_t ld,
+                                 const void* ring_workspace, int64_t ring_workspace_bytes, int64_t corners,
+                                 int32_t* ring_offset, int32_t* ring_value, int64_t* ring_area2,
+                                 int64_t ring_capacity, int32_t* vertices, int64_t vertex_capacity,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
