@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import transforms as T
+from .._lib import TrainImageDesc
 
 PRECISION_BITS = 22          # PIL Resample.c: 32 - 8 - 2
 N_CANDIDATES = 10            # RandomCrop_CategoryAreaConstraint's draws
@@ -278,13 +279,8 @@ def reference_apply(params: TrainParams, image: np.ndarray, label: np.ndarray, *
 
 # ------------------------------------------------------------------------------------------------ packing
 # include/catseg_hip_train.h CatsegTrainImageDesc
-DESC_DTYPE = np.dtype([("img_off", "<i8"), ("lab_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("nh", "<i4"), ("nw", "<i4"),
-                       ("xb_off", "<i4"), ("xk_off", "<i4"), ("kx", "<i4"), ("yb_off", "<i4"), ("yk_off", "<i4"),
-                       ("ky", "<i4"), ("nx_off", "<i4"), ("ny_off", "<i4"), ("crop", "<i4", (4,)), ("crop_sel", "<i4"),
-                       ("flip", "<i4"), ("lab_bytes", "<i4"), ("bright", "<i4"), ("order", "<i4"), ("contrast", "<i4"),
-                       ("sat", "<i4"), ("hue", "<i4"), ("hue_delta", "<i4"), ("beta", "<f4"), ("c_alpha", "<f4"),
-                       ("s_alpha", "<f4")])
-assert DESC_DTYPE.itemsize == 128
+DESC_DTYPE = np.dtype(TrainImageDesc)
+assert DESC_DTYPE.itemsize == 128        # the header's own promise
 DESC_WORDS = DESC_DTYPE.itemsize // 4
 PLANE_ALIGN = 64
 

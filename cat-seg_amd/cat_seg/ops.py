@@ -1158,7 +1158,7 @@ def region_outlines(ids, *, connectivity=8):
 TRAIN_INPUT_MAX_LABELS = 4096
 
 
-def _train_input_args(src, meta, B, desc_words=32):
+def _train_input_args(src, meta, B, desc_words=C.sizeof(L.TrainImageDesc) // 4):
     assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.data_ptr() % 16 == 0
     assert meta.is_cuda and meta.dtype == torch.int32 and meta.is_contiguous() and meta.data_ptr() % 8 == 0
     assert B > 0 and meta.numel() >= B * desc_words

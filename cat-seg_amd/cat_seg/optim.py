@@ -22,12 +22,6 @@ from . import _lib as L
 from .ops import _stream, call
 
 
-class _Desc(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                ("numel", C.c_int64), ("lr", C.c_float), ("weight_decay", C.c_float),
-                ("bias_correction1", C.c_float), ("bias_correction2", C.c_float)]
-
-
 def chunk_table(numels: List[int]) -> torch.Tensor:
     """The (tensor << 40 | chunk) table of catseg_adamw_step (host, int64)."""
     arr = (C.c_int64 * len(numels))(*numels)
@@ -88,13 +82,13 @@ class AdamW(torch.optim.Optimizer):
             self._table = chunk_table(list(key)).to(dev)
             self._table_key = key
             self._ws = torch.empty(self._table.numel(), device=dev, dtype=torch.float32)
-        descs = (_Desc * len(entries))()
+        descs = (L.AdamWTensor * len(entries))()
         for i, (p, st, lr, wd, bc1, bc2) in enumerate(entries):
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
             if g is not p.grad:
                 p.grad = g
-            descs[i] = _Desc(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                             p.numel(), lr, wd, bc1, bc2)
+            descs[i] = L.AdamWTensor(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                                     p.numel(), lr, wd, bc1, bc2)
         raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev, non_blocking=False)
         clip = self.max_grad_norm > 0
         if clip and self._norm is None:
