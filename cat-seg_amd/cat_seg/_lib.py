@@ -5,7 +5,8 @@ shared object is missing, and `require_gpu()` fails when no HIP device is
 visible, so nothing on the path can silently run elsewhere.
 
 The headers are the one definition of the ABI: `parse_abi` reads them once at import and
-makes every struct class, enum constant, argument list and return type from them.  A
+makes every struct class, enum constant, argument list and return type from them (the product
+headers, the tuning header, and the function-only headers catseg_hip.h includes).  A
 declaration it does not understand is an error, never a skipped entry.
 """
 from __future__ import annotations
@@ -19,6 +20,8 @@ LIB_PATH = os.environ.get("CATSEG_HIP_LIB", os.path.join(_HERE, "libcatseg_hip.s
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
 PRODUCT_HEADERS = ("catseg_hip.h", "catseg_hip_train.h")
 TUNING_HEADER = "catseg_hip_tuning.h"          # diagnostics entry, not part of the product ABI
+# product entries declared in headers of their own, which catseg_hip.h includes (the outline simplifier)
+INCLUDED_HEADERS = ("catseg_hip_simplify.h",)
 
 BIG = 1 << 62
 
@@ -120,7 +123,27 @@ def _read_headers():
     return structs, enums, protos, exported
 
 
+def _read_included_headers(structs):
+    protos = {}
+    for h in INCLUDED_HEADERS:
+        path = os.path.join(INCLUDE_DIR, h)
+        if not os.path.exists(path):
+            raise RuntimeError(f"{h} not found at {path}: catseg_hip.h includes it")
+        try:
+            more, enums, p = parse_abi(open(path).read(), structs)
+        except RuntimeError as err:
+            raise RuntimeError(f"{path}: {err}") from None
+        if len(more) != len(structs) or enums or set(p) & set(protos):
+            raise RuntimeError(f"{path}: an included header declares functions only, each once")
+        protos.update(p)
+    return protos
+
+
 _STRUCTS, _ENUMS, _PROTOS, EXPORTED = _read_headers()
+_INCLUDED_PROTOS = _read_included_headers(_STRUCTS)
+if set(_INCLUDED_PROTOS) & set(_PROTOS):
+    raise RuntimeError(f"declared twice: {sorted(set(_INCLUDED_PROTOS) & set(_PROTOS))}")
+EXPORTED_INCLUDED = tuple(_INCLUDED_PROTOS)
 # the struct classes under their header names without the prefix: RowMap, GemmArgs, RowsEpi, AdamWTensor, ...
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})
 F32, BF16, FP8 = (_ENUMS["CATSEG_" + n] for n in ("F32", "BF16", "FP8"))
@@ -147,7 +170,7 @@ def load() -> C.CDLL:
             f"libcatseg_hip.so not found at {LIB_PATH}: build it with "
             "`make -C cat-seg_amd/csrc` (or __graft_entry__.build()); the CAT-Seg HIP path has no fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _PROTOS.items():
+    for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

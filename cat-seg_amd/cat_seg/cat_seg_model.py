@@ -14,8 +14,9 @@ this boundary returns one result per input image by default
 With MODEL.CATSEG_HIP.TILED.ENABLED an image of any size is segmented at its own resolution: cut into
 tiles, each through the network as an image of its own, merged on the device (engine.forward_tiled).
 With MODEL.CATSEG_HIP.REGIONS.ENABLED (OUTPUT "labels") every returned label map is sieved (MIN_AREA) and
-described by "sem_seg_regions" + "regions_info" on the device (CATSeg.add_regions; ops.label_regions), and with
-REGIONS.OUTLINES by "regions_outlines", the regions' boundaries as polygon rings (ops.region_outlines).
+described by "sem_seg_regions" + "regions_info" on the device (CATSeg.add_regions; ops.label_regions), with
+REGIONS.OUTLINES by "regions_outlines", the regions' boundaries as polygon rings (ops.region_outlines), and with
+REGIONS.SIMPLIFY.ENABLED by "regions_outlines_simplified", those rings simplified arc by arc (ops.simplify_outlines).
 
 Everything between the input copy and the returned tensors runs in the HIP kernels of
 libcatseg_hip.so through `CatSegEngine`; there is no CPU or PyTorch-op fallback.
@@ -76,7 +77,8 @@ class CATSeg(nn.Module):
                  vit_fp8: bool = False, graph: bool = True, output: str = "probs", tiled: bool = False,
                  tiled_tile: int = 384, tiled_stride: int = 256, tiled_batch: int = 8, tta_merge: str = "host",
                  tiled_window: str = "uniform", tiled_global: bool = False, regions: bool = False,
-                 regions_connectivity: int = 8, regions_min_area: int = 0, regions_outlines: bool = False):
+                 regions_connectivity: int = 8, regions_min_area: int = 0, regions_outlines: bool = False,
+                 regions_simplify: bool = False, regions_simplify_tolerance: float = 1.0):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
@@ -95,6 +97,15 @@ class CATSeg(nn.Module):
         if self.regions_outlines and not self.regions:
             raise ValueError("CATSeg: MODEL.CATSEG_HIP.REGIONS.OUTLINES traces the regions of "
                              "MODEL.CATSEG_HIP.REGIONS.ENABLED, which is off")
+        # the outlines simplified arc by arc (MODEL.CATSEG_HIP.REGIONS.SIMPLIFY; ops.simplify_outlines)
+        self.regions_simplify = bool(regions_simplify)
+        self.regions_simplify_tolerance = float(regions_simplify_tolerance)
+        if self.regions_simplify and not self.regions_outlines:
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.REGIONS.SIMPLIFY.ENABLED simplifies the rings of "
+                             "MODEL.CATSEG_HIP.REGIONS.OUTLINES, which is off")
+        if self.regions_simplify and not 0.0 <= self.regions_simplify_tolerance <= ops.SIMPLIFY_MAX_SIDE:
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.REGIONS.SIMPLIFY.TOLERANCE must be in "
+                             f"[0, {ops.SIMPLIFY_MAX_SIDE}] pixels, got {regions_simplify_tolerance!r}")
         # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
         self.tiled = bool(tiled)
         self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
@@ -186,6 +197,8 @@ class CATSeg(nn.Module):
             "regions_connectivity": int(regions.get("CONNECTIVITY", 8)),
             "regions_min_area": int(regions.get("MIN_AREA", 0)),
             "regions_outlines": bool(regions.get("OUTLINES", False)),
+            "regions_simplify": bool((regions.get("SIMPLIFY", None) or {}).get("ENABLED", False)),
+            "regions_simplify_tolerance": float((regions.get("SIMPLIFY", None) or {}).get("TOLERANCE", 1.0)),
         }
 
     # ------------------------------------------------------------------ parameters
@@ -301,7 +314,9 @@ class CATSeg(nn.Module):
         "sem_seg_regions" (the region numbers) and "regions_info" (label, area, bbox, first, score = the mean
         of "sem_seg_score" over the region) describe the returned map.  With REGIONS.OUTLINES, "regions_outlines" =
         ops.region_outlines of "sem_seg_regions" (two more 4-byte reads: corners, rings): ring_value is a region
-        number, every region has one exterior ring, and they come in region order.  A no-op with REGIONS.ENABLED
+        number, every region has one exterior ring, and they come in region order.  With REGIONS.SIMPLIFY.ENABLED,
+        "regions_outlines_simplified" = ops.simplify_outlines of those rings under SIMPLIFY.TOLERANCE (two more
+        4-byte reads: nodes, kept vertices); "regions_outlines" stays as it is.  A no-op with REGIONS.ENABLED
         False."""
         if not self.regions:
             return result
@@ -313,6 +328,9 @@ class CATSeg(nn.Module):
         out = {**result, "sem_seg_labels": labels, "sem_seg_regions": ids, "regions_info": table}
         if self.regions_outlines:
             out["regions_outlines"] = ops.region_outlines(ids, connectivity=conn)
+            if self.regions_simplify:
+                out["regions_outlines_simplified"] = ops.simplify_outlines(ids, out["regions_outlines"],
+                                                                           self.regions_simplify_tolerance)
         return out
 
     def _forward_traced(self, batched_inputs: List[dict]):

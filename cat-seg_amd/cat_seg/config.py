@@ -227,4 +227,10 @@ def add_cat_seg_config(cfg):
     # REGIONS.ENABLED only: "regions_outlines" = ops.region_outlines of "sem_seg_regions" under CONNECTIVITY, the
     # regions' boundaries as polygon rings on the device (cat_seg.vectorize turns them into GeoJSON)
     cfg.MODEL.CATSEG_HIP.REGIONS.OUTLINES = False
+    # REGIONS.OUTLINES only: "regions_outlines_simplified" = ops.simplify_outlines of "regions_outlines", Douglas-
+    # Peucker with TOLERANCE (pixels, 0 .. 16384) on the device, arc by arc, so neighbours share their simplified
+    # boundary; "regions_outlines" stays as it is
+    cfg.MODEL.CATSEG_HIP.REGIONS.SIMPLIFY = C()
+    cfg.MODEL.CATSEG_HIP.REGIONS.SIMPLIFY.ENABLED = False
+    cfg.MODEL.CATSEG_HIP.REGIONS.SIMPLIFY.TOLERANCE = 1.0
     return cfg

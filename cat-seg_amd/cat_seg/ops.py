@@ -1155,6 +1155,132 @@ def region_outlines(ids, *, connectivity=8):
     return region_outlines_write(ids, rws, K, out)
 
 
+SIMPLIFY_MAX_SIDE = 16384
+_OUTLINE_KEYS = (("ring_offset", torch.int32), ("ring_value", torch.int32), ("ring_area2", torch.int64),
+                 ("vertices", torch.int32))
+
+
+def _simplify_args(ids, outlines, what="simplify_outlines"):
+    """(H, W, ld, NR, K) of a map and the rings `region_outlines` made for it."""
+    H, W, ld = _label_map_args(ids, what)
+    if H > SIMPLIFY_MAX_SIDE or W > SIMPLIFY_MAX_SIDE:
+        raise ValueError(f"{what}: a {H} x {W} map exceeds H, W <= {SIMPLIFY_MAX_SIDE} (the scores are exact int64)")
+    for k, dt in _OUTLINE_KEYS:
+        t = outlines[k]
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == ids.device):
+            raise ValueError(f"{what}: outlines[{k!r}] must be a contiguous {dt} CUDA tensor on the map's device")
+    off, val, a2, vert = (outlines[k] for k, _ in _OUTLINE_KEYS)
+    NR = val.numel()
+    if off.dim() != 1 or val.dim() != 1 or tuple(off.shape) != (NR + 1,) or tuple(a2.shape) != (NR,):
+        raise ValueError(f"{what}: ring_offset must have one element more than ring_value and ring_area2")
+    if vert.dim() != 2 or vert.shape[1] != 2:
+        raise ValueError(f"{what}: vertices must be (K, 2), got {tuple(vert.shape)}")
+    K = vert.shape[0]
+    if not (1 <= NR <= K <= 4 * (H + 1) * (W + 1)):
+        raise ValueError(f"{what}: {NR} rings and {K} corners are not the outlines of a {H} x {W} map")
+    return H, W, ld, NR, K
+
+
+def _simplify_workspace(H, W, K, nodes, device, what="simplify_outlines"):
+    nbytes = L.load().catseg_outline_simplify_workspace(H, W, K, int(nodes))
+    if nbytes <= 0:
+        raise ValueError(f"{what}: no workspace for a {H} x {W} map with {K} corners" +
+                         (f" and {nodes} nodes (corners <= nodes <= 4 (H + 1) (W + 1))" if nodes >= 0 else ""))
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device), nbytes
+
+
+def _simplify_tolerance(tolerance, what="simplify_outlines"):
+    t = float(tolerance)
+    if not 0.0 <= t <= SIMPLIFY_MAX_SIDE:                     # refuses NaN too
+        raise ValueError(f"{what}: tolerance must be in [0, {SIMPLIFY_MAX_SIDE}] pixels, got {tolerance!r}")
+    return t
+
+
+def simplify_outlines_count(ids, outlines):
+    """Junction + node-count third of `simplify_outlines` (catseg_outline_simplify_count): returns the int32 map
+    workspace, whose element 0 is the number of nodes N (still on the device).  No host synchronisation."""
+    H, W, ld, NR, K = _simplify_args(ids, outlines)
+    ws, nbytes = _simplify_workspace(H, W, K, -1, ids.device)
+    with _rec("outline_simplify_count", 0, 4 * H * W + 8 * K + nbytes):
+        call("catseg_outline_simplify_count", ids.data_ptr(), H, W, ld, outlines["ring_offset"].data_ptr(), NR,
+             outlines["vertices"].data_ptr(), K, ws.data_ptr(), nbytes, _stream())
+    return ws
+
+
+def simplify_outlines_run(ids, outlines, ws, nodes, tolerance):
+    """Node, arc and Douglas-Peucker third of `simplify_outlines` (catseg_outline_simplify_run): with the map
+    workspace `ws` of `simplify_outlines_count` and nodes = N read from it, returns the int32 node workspace, whose
+    element 1 is the number of kept vertices K' (still on the device).  No host synchronisation."""
+    H, W, ld, NR, K = _simplify_args(ids, outlines)
+    t = _simplify_tolerance(tolerance)
+    nodes = int(nodes)
+    assert ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous()
+    nws, nbytes = _simplify_workspace(H, W, K, nodes, ids.device)
+    with _rec("outline_simplify_run", 0, ws.numel() * 4 + 8 * K + nbytes):
+        call("catseg_outline_simplify_run", outlines["ring_offset"].data_ptr(), NR, outlines["vertices"].data_ptr(), K,
+             H, W, t, ws.data_ptr(), ws.numel() * 4, nodes, nws.data_ptr(), nbytes, _stream())
+    return nws
+
+
+def simplify_outlines_write(ids, outlines, nws, nodes, out):
+    """Write third of `simplify_outlines` (catseg_outline_simplify_write): with the node workspace `nws` of
+    `simplify_outlines_run` for the same nodes, fills `out`, a dict of device tensors "ring_offset" (capacity + 1,)
+    int32, "ring_value" (capacity,) int32, "ring_area2" (capacity,) int64, "ring_hole" (capacity,) uint8 and
+    "vertices" (vertex capacity, 2) int32: rings below min(NR, capacity) and vertices below the vertex capacity;
+    nothing is stored beyond either.  No host synchronisation."""
+    what = "simplify_outlines"
+    H, W, ld, NR, K = _simplify_args(ids, outlines)
+    nodes = int(nodes)
+    assert nws.is_cuda and nws.dtype == torch.int32 and nws.is_contiguous()
+    for k, dt in _OUTLINE_KEYS + (("ring_hole", torch.uint8),):
+        t = out[k]
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise ValueError(f"{what}: out[{k!r}] must be a contiguous {dt} CUDA tensor")
+    off, val, a2, hole, vert = (out[k] for k in ("ring_offset", "ring_value", "ring_area2", "ring_hole", "vertices"))
+    cap = val.numel()
+    if (off.dim() != 1 or val.dim() != 1 or tuple(off.shape) != (cap + 1,) or tuple(a2.shape) != (cap,)
+            or tuple(hole.shape) != (cap,)):
+        raise ValueError(f"{what}: ring_offset must have one element more than ring_value, ring_area2 and ring_hole")
+    if vert.dim() != 2 or vert.shape[1] != 2:
+        raise ValueError(f"{what}: vertices must be (capacity, 2), got {tuple(vert.shape)}")
+    with _rec("outline_simplify_write", 0, nws.numel() * 4 + 17 * cap + 8 * vert.shape[0]):
+        call("catseg_outline_simplify_write", nws.data_ptr(), nws.numel() * 4, H, W, K, nodes, NR,
+             outlines["ring_value"].data_ptr(), outlines["ring_area2"].data_ptr(), off.data_ptr(),
+             val.data_ptr() or None, a2.data_ptr() or None, hole.data_ptr() or None, cap, vert.data_ptr() or None,
+             vert.shape[0], _stream())
+    return out
+
+
+def simplify_outlines(ids, outlines, tolerance):
+    """The rings of `region_outlines(ids)` simplified by Douglas-Peucker with `tolerance` (pixels, 0 .. 16384) on the
+    device, arc by arc (catseg_outline_simplify_*; DESIGN.md section 4, "Outline simplification"): the boundary
+    between two regions is one arc between two junctions (vertices where at least 3 boundary edges meet, and the
+    map's corners), so both neighbours keep the same vertices and no sliver or gap opens between them.  Junctions are
+    always kept, also where they lie inside a straight edge of a ring (a T-junction), so a ring can gain vertices
+    over its source.  ids: the 2-D int32 CUDA map (H, W <= 16384), possibly a row-strided view; outlines: the dict
+    `region_outlines` returned for it.  Returns a dict of device tensors, allocated exactly: the same NR rings in the
+    same order, "ring_offset" (NR + 1,) int32, "ring_value" (NR,) int32 (copied), "ring_area2" (NR,) int64 (the
+    shoelace sum of the kept vertices; may be 0 or change sign), "ring_hole" (NR,) uint8 (1 where the source ring's
+    ring_area2 < 0) and "vertices" (K', 2) int32.  A ring may end with 1 or 2 vertices.  Crossings at large
+    tolerances are not prevented, and areas are not preserved.
+
+    Two synchronising 4-byte reads (N, then K') size the buffers.  Not registered as a torch.ops.catseg.* custom op:
+    the output sizes depend on the data."""
+    H, W, ld, NR, K = _simplify_args(ids, outlines)
+    _simplify_tolerance(tolerance)
+    ws = simplify_outlines_count(ids, outlines)
+    N = int(ws[0].item())
+    nws = simplify_outlines_run(ids, outlines, ws, N, tolerance)
+    K2 = int(nws[1].item())
+    dev = ids.device
+    out = {"ring_offset": torch.empty(NR + 1, dtype=torch.int32, device=dev),
+           "ring_value": torch.empty(NR, dtype=torch.int32, device=dev),
+           "ring_area2": torch.empty(NR, dtype=torch.int64, device=dev),
+           "ring_hole": torch.empty(NR, dtype=torch.uint8, device=dev),
+           "vertices": torch.empty(K2, 2, dtype=torch.int32, device=dev)}
+    return simplify_outlines_write(ids, outlines, nws, N, out)
+
+
 TRAIN_INPUT_MAX_LABELS = 4096
 
 

@@ -710,4 +710,8 @@ int catseg_region_outlines_write(const int32_t* ids, int64_t H, int64_t W, int64
 #ifdef __cplusplus
 }
 #endif
+
+/* catseg_outline_simplify_*: the outlines above simplified arc by arc, declared in a header of their own */
+#include "catseg_hip_simplify.h"
+
 #endif /* CATSEG_HIP_H */
