@@ -22,10 +22,12 @@ PRODUCT_HEADERS = ("catseg_hip.h", "catseg_hip_train.h")
 TUNING_HEADER = "catseg_hip_tuning.h"          # diagnostics entry, not part of the product ABI
 # product entries declared in headers of their own, which catseg_hip.h includes (the outline simplifier)
 INCLUDED_HEADERS = ("catseg_hip_simplify.h",)
+# later function-only headers catseg_hip.h includes, a group of their own (the boundary-aware evaluation)
+EXTENSION_HEADERS = ("catseg_hip_boundary.h",)
 
 BIG = 1 << 62
 
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint8_t": C.c_uint8,
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "int16_t": C.c_int16,
             "float": C.c_float, "double": C.c_double}
 # catseg_hip_train.h says of each: "an array of these lives in DEVICE memory".  The host fills them as
 # bytes and passes a device address, so a pointer to one is a plain c_void_p, not POINTER(cls).
@@ -123,9 +125,9 @@ def _read_headers():
     return structs, enums, protos, exported
 
 
-def _read_included_headers(structs):
+def _read_included_headers(structs, headers=INCLUDED_HEADERS):
     protos = {}
-    for h in INCLUDED_HEADERS:
+    for h in headers:
         path = os.path.join(INCLUDE_DIR, h)
         if not os.path.exists(path):
             raise RuntimeError(f"{h} not found at {path}: catseg_hip.h includes it")
@@ -144,6 +146,10 @@ _INCLUDED_PROTOS = _read_included_headers(_STRUCTS)
 if set(_INCLUDED_PROTOS) & set(_PROTOS):
     raise RuntimeError(f"declared twice: {sorted(set(_INCLUDED_PROTOS) & set(_PROTOS))}")
 EXPORTED_INCLUDED = tuple(_INCLUDED_PROTOS)
+_EXTENSION_PROTOS = _read_included_headers(_STRUCTS, EXTENSION_HEADERS)
+if set(_EXTENSION_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS)):
+    raise RuntimeError(f"declared twice: {sorted(set(_EXTENSION_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS)))}")
+EXPORTED_EXTENSIONS = tuple(_EXTENSION_PROTOS)
 # the struct classes under their header names without the prefix: RowMap, GemmArgs, RowsEpi, AdamWTensor, ...
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})
 F32, BF16, FP8 = (_ENUMS["CATSEG_" + n] for n in ("F32", "BF16", "FP8"))
@@ -170,7 +176,7 @@ def load() -> C.CDLL:
             f"libcatseg_hip.so not found at {LIB_PATH}: build it with "
             "`make -C cat-seg_amd/csrc` (or __graft_entry__.build()); the CAT-Seg HIP path has no fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS}.items():
+    for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS, **_EXTENSION_PROTOS}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

@@ -22,6 +22,12 @@ column-major label runs of the argmax map, made on the device (`ops.label_runs`,
 catseg_label_runs_*): only the runs cross to the host, where `rle_records_from_runs` reads every
 label's RLE off them; `rle="host"` copies the map and encodes one mask per label as the reference
 does.  Both give the same records and the same file.
+
+With `boundary=[...]` the evaluators also report boundary-aware metrics (Boundary IoU, trimap and
+eroded-boundary mIoU / pACC / mF1 per width; no counterpart in the reference): `process()` bins their
+counters on the device from the argmax map and the ground truth (`ops.boundary_confusion`:
+catseg_boundary_distance of both maps + catseg_boundary_confusion) and `evaluate()` forms
+`boundary_metrics` from the reduced counters.  Without it nothing changes.
 """
 from __future__ import annotations
 
@@ -185,8 +191,93 @@ def semseg_metrics(conf: np.ndarray, class_names: Sequence[str], val_extra_class
     return res
 
 
+def boundary_specs(boundary) -> list:
+    """The `boundary=` argument of the evaluators as a list of (kind, value, tag): ("px", n) is an absolute
+    width of n pixels, tag "{n}px"; ("ratio", r) the per-image width max(1, round(r * image diagonal)), tag
+    "{r:g}d".  Up to 8 specs; a bad one raises ValueError."""
+    specs = []
+    if isinstance(boundary, (str, bytes)) or not hasattr(boundary, "__iter__"):
+        raise ValueError(f"boundary must be a sequence of ('px', n) / ('ratio', r) specs, got {boundary!r}")
+    for spec in boundary:
+        if not isinstance(spec, (tuple, list)) or len(spec) != 2 or spec[0] not in ("px", "ratio"):
+            raise ValueError(f"boundary spec {spec!r}: expected ('px', n) or ('ratio', r)")
+        kind, v = spec
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"boundary spec {spec!r}: the width must be a number")
+        if kind == "px":
+            if int(v) != v or not 1 <= int(v) <= 16383:
+                raise ValueError(f"boundary spec {spec!r}: a pixel width is an integer in 1 .. 16383")
+            specs.append(("px", int(v), f"{int(v)}px"))
+        else:
+            if not (v > 0 and v < 1):        # also refuses NaN
+                raise ValueError(f"boundary spec {spec!r}: a ratio of the image diagonal lies in (0, 1)")
+            specs.append(("ratio", float(v), f"{float(v):g}d"))
+    if not 1 <= len(specs) <= 8:
+        raise ValueError(f"boundary: 1 .. 8 specs, got {len(specs)}")
+    tags = [s[2] for s in specs]
+    if len(set(tags)) != len(tags):
+        raise ValueError(f"boundary: two specs share a tag: {tags}")
+    return specs
+
+
+def boundary_widths(specs, H: int, W: int) -> list:
+    """The widths in pixels of `boundary_specs` for an H x W image (a ratio: max(1, round(r * sqrt(H^2 + W^2))),
+    at most 16383)."""
+    return [v if kind == "px" else min(16383, max(1, int(round(v * float(np.sqrt(float(H) ** 2 + float(W) ** 2))))))
+            for kind, v, _ in specs]
+
+
+def boundary_metrics(conf, counters, class_names: Sequence[str], tags: Sequence[str]) -> dict:
+    """The boundary-aware metrics from the (N+1) x (N+1) confusion matrix and the reduced counters of
+    catseg_boundary_confusion (K ((N+1)^2 + 3N) integers; per width band_conf, inter, gt_band, pred_band), one
+    width per tag t:
+      BIoU@t-<class> = 100 inter / (gt_band + pred_band - inter), NaN where gt_band == 0; mBIoU@t their mean
+      over the classes with gt_band > 0 (Boundary IoU, the counts accumulated over the dataset);
+      trimap-mIoU@t, trimap-pACC@t = semseg_metrics of band_conf (the pixels within the width of a ground-truth
+      class boundary); eroded-mIoU@t, eroded-pACC@t = semseg_metrics of conf - band_conf (those pixels left
+      out), eroded-mF1@t = the mean over the classes seen in that matrix's ground truth of
+      100 * 2 tp / (pos_gt + pos_pred).
+    An empty band or an empty eroded map gives NaN, without a warning."""
+    conf = np.asarray(conf, dtype=np.int64)
+    n, n1 = len(class_names), len(class_names) + 1
+    per = n1 * n1 + 3 * n
+    counters = np.asarray(counters, dtype=np.int64).reshape(-1)
+    if conf.shape != (n1, n1) or counters.size != len(tags) * per:
+        raise ValueError(f"boundary_metrics: conf {conf.shape} / {counters.size} counters do not match {n} classes "
+                         f"and {len(tags)} widths")
+    nan = float("nan")
+    res = {}
+
+    def mean(v, seen):
+        return float(v[seen].mean()) if seen.any() else nan
+
+    for k, t in enumerate(tags):
+        c = counters[k * per:(k + 1) * per]
+        band = c[:n1 * n1].reshape(n1, n1)
+        inter, gt_band, pred_band = (c[n1 * n1 + i * n:n1 * n1 + (i + 1) * n].astype(np.float64) for i in range(3))
+        seen = gt_band > 0
+        biou = np.where(seen, 100 * inter / np.where(seen, gt_band + pred_band - inter, 1.0), nan)
+        res[f"mBIoU@{t}"] = mean(biou, seen)
+        res.update({f"BIoU@{t}-{name}": float(biou[i]) for i, name in enumerate(class_names)})
+        for prefix, m in (("trimap", band), ("eroded", conf - band)):
+            if m[:-1, :-1].sum() > 0:
+                sm = semseg_metrics(m, class_names)
+                res[f"{prefix}-mIoU@{t}"], res[f"{prefix}-pACC@{t}"] = float(sm["mIoU"]), float(sm["pACC"])
+            else:
+                res[f"{prefix}-mIoU@{t}"] = res[f"{prefix}-pACC@{t}"] = nan
+        core = (conf - band)[:-1, :-1].astype(np.float64)
+        tp, pos_gt, pos_pred = np.diagonal(core), core.sum(axis=0), core.sum(axis=1)
+        gseen = pos_gt > 0
+        res[f"eroded-mF1@{t}"] = mean(np.where(gseen, 100 * 2 * tp / np.where(gseen, pos_gt + pos_pred, 1.0), nan), gseen)
+    return res
+
+
 class SemSegEvaluator:
     """reset() / process(inputs, outputs) / evaluate() -> {"sem_seg": metrics}.
+
+    `boundary`: None, or up to 8 width specs (`boundary_specs`) that turn the boundary-aware metrics on:
+    Boundary IoU, trimap and eroded-boundary mIoU / pACC / mF1 per width (`boundary_metrics`), their counters
+    binned on the device from the same maps (ops.boundary_confusion) and added to the "sem_seg" dict.
 
     Ground truth per input: `input["sem_seg_gt"]` (H x W labels, tensor or array), else
     `gt_loader(input)` (e.g. reading `input["file_name"]`'s `sem_seg_file_name` as the
@@ -197,10 +288,11 @@ class SemSegEvaluator:
 
     def __init__(self, dataset_name: Optional[str] = None, distributed: bool = True, output_dir=None, *,
                  class_names: Optional[Sequence[str]] = None, ignore_label: Optional[int] = None,
-                 gt_loader: Optional[Callable] = None, device=None, rle: str = "device"):
+                 gt_loader: Optional[Callable] = None, device=None, rle: str = "device", boundary=None):
         if rle not in ("device", "host"):
             raise ValueError(f"SemSegEvaluator: rle must be 'device' or 'host', got {rle!r}")
         self._rle = rle
+        self._boundary = boundary_specs(boundary) if boundary is not None else None
         meta = _metadata(dataset_name)
         if class_names is None:
             class_names = meta.get("stuff_classes") if meta is not None else None
@@ -226,6 +318,22 @@ class SemSegEvaluator:
         self._conf = torch.zeros(n1 * n1, dtype=torch.int64, device=self._device)
         self._invalid = torch.zeros(1, dtype=torch.int64, device=self._device)
         self._predictions = []
+        if self._boundary is not None:
+            n = self._num_classes
+            self._bcounters = torch.zeros(len(self._boundary) * (n1 * n1 + 3 * n), dtype=torch.int64,
+                                          device=self._device)
+
+    @property
+    def boundary_tags(self) -> list:
+        """The width tags of `boundary=`, in order (empty without it)."""
+        return [s[2] for s in self._boundary] if self._boundary is not None else []
+
+    def _boundary_update(self, labels, gt):
+        """The boundary counters of one image from its int32 prediction map (the fold is applied on the device)."""
+        H, W = labels.shape
+        ops.boundary_confusion(labels, gt, boundary_widths(self._boundary, H, W), self._bcounters,
+                               num_classes=self._num_classes, ignore_label=self._ignore_label,
+                               clamp_pred=self.clamp_pred)
 
     def _gt(self, inp) -> torch.Tensor:
         gt = inp.get("sem_seg_gt")
@@ -254,10 +362,15 @@ class SemSegEvaluator:
                 raise ValueError(f"gt {tuple(gt.shape)} vs prediction {tuple(probs.shape[1:])}")
             ops.semseg_confusion(probs, gt, self._conf, self._invalid, num_classes=self._num_classes,
                                  ignore_label=self._ignore_label, clamp_pred=self.clamp_pred)
-            if self._output_dir and self._rle == "device":
+            device_rle = bool(self._output_dir) and self._rle == "device"
+            # the argmax map: for the boundary counters and for the label runs of the records
+            labels = probs.argmax(dim=0).to(torch.int32) if device_rle or self._boundary is not None else None
+            if self._boundary is not None:
+                self._boundary_update(labels, gt)
+            if device_rle:
                 # the records are written only with an output_dir (the reference builds them for every
                 # image); only the label runs of the argmax map are brought to the host
-                self._records_from_device(probs.argmax(dim=0).to(torch.int32), inp.get("file_name"))
+                self._records_from_device(labels, inp.get("file_name"))
             elif self._output_dir:
                 pred = probs.argmax(dim=0)
                 if self.clamp_pred >= 0:
@@ -273,6 +386,8 @@ class SemSegEvaluator:
             raise ValueError(f"gt {tuple(gt.shape)} vs label map {tuple(labels.shape)}")
         ops.semseg_confusion_labels(labels, gt, self._conf, self._invalid, num_classes=self._num_classes,
                                     ignore_label=self._ignore_label, clamp_pred=self.clamp_pred)
+        if self._boundary is not None:
+            self._boundary_update(labels, gt)
         if self._output_dir and self._rle == "device":
             self._records_from_device(labels, inp.get("file_name"))
         elif self._output_dir:
@@ -337,6 +452,9 @@ class SemSegEvaluator:
             # the reference's bincount would outgrow the matrix and its reshape would fail
             raise ValueError(f"{invalid} ground-truth labels outside [0, {self._num_classes}) and != ignore_label")
         conf = self.confusion_matrix()
+        bcounters = None
+        if self._boundary is not None:
+            bcounters = (reduce_confusion(self._bcounters) if self._distributed else self._bcounters.cpu()).numpy()
         preds = self.predictions() if self._output_dir else None
         if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
             return None
@@ -347,6 +465,8 @@ class SemSegEvaluator:
             with open(os.path.join(self._output_dir, "sem_seg_predictions.json"), "w") as f:
                 f.write(json.dumps(preds))
         res = self._metrics(conf)
+        if bcounters is not None:
+            res.update(boundary_metrics(conf, bcounters, self._class_names, [s[2] for s in self._boundary]))
         if self._output_dir:
             torch.save(res, os.path.join(self._output_dir, "sem_seg_evaluation.pth"))
         return OrderedDict({"sem_seg": res})

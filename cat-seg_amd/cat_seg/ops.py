@@ -909,6 +909,54 @@ def _label_map_args(labels, what):
     return H, W, ld
 
 
+def boundary_distance(labels, cap, *, clamp_pred=-1, out=None):
+    """min(D, cap) of a label map as int16 (catseg_boundary_distance; DESIGN.md section 4, "Boundary-aware
+    evaluation"): D(p) = the Chebyshev distance from p to the nearest pixel of another label, the outside of the
+    map counting as one (D >= 1; labels >= clamp_pred compare as clamp_pred, clamp_pred < 0: no fold).  labels:
+    2-D int32 CUDA tensor, rows may be strided; out: (H, W) int16 (fresh when None), rows may be strided.
+    Returns out.  No host synchronisation."""
+    H, W, ld = _label_map_args(labels, "boundary_distance")
+    nbytes = L.load().catseg_boundary_distance_workspace(H, W, int(cap))
+    if nbytes <= 0:
+        raise ValueError(f"boundary_distance: H, W and cap must lie in 1 .. 16384, got {H} x {W}, cap {cap!r}")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int16, device=labels.device)
+    if (not torch.is_tensor(out) or out.device != labels.device or out.dtype != torch.int16
+            or tuple(out.shape) != (H, W) or (W > 1 and out.stride(1) != 1)):
+        raise ValueError("boundary_distance: out must be an (H, W) int16 tensor on the map's device with contiguous rows")
+    ld_out = out.stride(0) if H > 1 else W
+    if ld_out < W:
+        raise ValueError(f"boundary_distance: row stride {ld_out} of out < W = {W}")
+    ws = torch.empty(nbytes // 2, dtype=torch.int16, device=labels.device)
+    # bytes: the map read by both passes, the row distances written and read back, the result written
+    with _rec("boundary_distance", 0, 8 * H * W + 2 * nbytes + 2 * H * W):
+        call("catseg_boundary_distance", labels.data_ptr(), H, W, ld, int(clamp_pred), int(cap), out.data_ptr(),
+             ld_out, ws.data_ptr(), nbytes, _stream())
+    return out
+
+
+def boundary_confusion(pred, gt, widths, counters, *, num_classes, ignore_label=255, clamp_pred=-1):
+    """counters += the boundary counters of one image (catseg_boundary_confusion): both distance maps
+    (`boundary_distance` with cap = max(widths) + 1; of pred folded by clamp_pred, of gt as it is), then per width
+    band_conf ((N+1)^2, [pred][gt]), inter, gt_band and pred_band (N each).  pred, gt: (H, W) int32 contiguous
+    CUDA maps; widths: 1 .. 8 ints in 1 .. 16383; counters: (K ((N+1)^2 + 3N),) int64.  Returns counters."""
+    H, W, _ = _label_map_args(pred, "boundary_confusion")
+    widths = [int(w) for w in widths]
+    if not 1 <= len(widths) <= 8 or min(widths) < 1 or max(widths) > 16383:
+        raise ValueError(f"boundary_confusion: 1 .. 8 widths in 1 .. 16383, got {widths}")
+    assert pred.is_contiguous() and gt.is_contiguous() and gt.shape == (H, W) and gt.dtype == torch.int32
+    assert gt.device == pred.device and counters.device == pred.device
+    K, n = len(widths), int(num_classes)
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() == K * ((n + 1) ** 2 + 3 * n)
+    cap = max(widths) + 1
+    dist_pred = boundary_distance(pred, cap, clamp_pred=clamp_pred)
+    dist_gt = boundary_distance(gt, cap)
+    with _rec("boundary_confusion", 0, 12 * H * W):
+        call("catseg_boundary_confusion", pred.data_ptr(), gt.data_ptr(), dist_pred.data_ptr(), dist_gt.data_ptr(),
+             H, W, n, int(ignore_label), int(clamp_pred), (C.c_int * K)(*widths), K, counters.data_ptr(), _stream())
+    return counters
+
+
 def label_runs_count(labels, *, clamp_pred=-1):
     """Count + scan half of `label_runs` (catseg_label_runs_count): returns the int32 workspace tensor, whose
     element 0 is the number of runs R (still on the device) and whose rest holds the write offsets."""

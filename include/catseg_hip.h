@@ -713,5 +713,7 @@ int catseg_region_outlines_write(const int32_t* ids, int64_t H, int64_t W, int64
 
 /* catseg_outline_simplify_*: the outlines above simplified arc by arc, declared in a header of their own */
 #include "catseg_hip_simplify.h"
+/* catseg_boundary_*: boundary distance of a label map and the counters of the boundary-aware metrics */
+#include "catseg_hip_boundary.h"
 
 #endif /* CATSEG_HIP_H */
