@@ -11,6 +11,8 @@ same config keys, with `forward(batched_inputs: list[dict]) -> list[dict]`:
 The reference returns results for batched_inputs[0] only (cat_seg_model.py:227-229);
 this boundary returns one result per input image by default
 (MODEL.CATSEG_HIP.RETURN_ALL_IMAGES; set False for the reference's exact behaviour).
+The output stage (CATSeg._finish) resizes a uniform batch (equal image sizes, equal output sizes) with one
+launch, with MODEL.CATSEG_HIP.GRAPH on or off, and its results are views of that launch's tensor.
 With MODEL.CATSEG_HIP.TILED.ENABLED an image of any size is segmented at its own resolution: cut into
 tiles, each through the network as an image of its own, merged on the device (engine.forward_tiled).
 With MODEL.CATSEG_HIP.REGIONS.ENABLED (OUTPUT "labels") every returned label map is sieved (MIN_AREA) and
@@ -48,6 +50,21 @@ _DTYPES = {"bf16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32}
 def _weights_version(params: Iterable[nn.Parameter]) -> int:
     """Sum of the parameters' in-place version counters: an optimizer step or a copy_ bumps it."""
     return sum(p._version for p in params)
+
+
+def returned_inputs(batched_inputs: List[dict], return_all_images: bool) -> List[dict]:
+    """The inputs that get a result: every one, or the first alone as the reference does."""
+    return batched_inputs if return_all_images else batched_inputs[:1]
+
+
+def output_plan(batched_inputs: List[dict], sizes, logits_hw, return_all_images: bool):
+    """What the output stage does per returned image, [((h, w), (crop_h, crop_w))]: the result's size (a dict's
+    "height" / "width", each defaulting to the image's own) and the region of the image's logits that the
+    resize reads (sem_seg_postprocess's crop to the image, at the logits' resolution).  `sizes`: the (h, w)
+    of every image; `logits_hw`: the logits' resolution.  Python ints in and out, so dynamo traces through it."""
+    h_l, w_l = logits_hw
+    return [((int(x.get("height", ih)), int(x.get("width", iw))), (min(h_l, ih), min(w_l, iw)))
+            for x, (ih, iw) in zip(returned_inputs(batched_inputs, return_all_images), sizes)]
 
 
 def convert_openai_clip_keys(sd: Dict[str, torch.Tensor], prefix: str = "") -> Dict[str, torch.Tensor]:
@@ -282,12 +299,9 @@ class CATSeg(nn.Module):
     # ------------------------------------------------------------------ forward
     def _batch(self, eng: CatSegEngine, images: List[torch.Tensor]):
         """Stage the images into one zero-padded fp32 canvas on the device (ImageList.from_tensors
-        geometry: batch max, rounded up to size_divisibility).  Host images go through one pinned
-        canvas and one H2D copy; images already on the device are copied in place there."""
-        d = max(self.size_divisibility, 1)
-        H = max(int(i.shape[-2]) for i in images)
-        W = max(int(i.shape[-1]) for i in images)
-        H, W = -(-H // d) * d, -(-W // d) * d
+        geometry, _canvas_geometry).  Host images go through one pinned canvas and one H2D copy;
+        images already on the device are copied in place there."""
+        H, W = self._canvas_geometry(images)
         dev = eng.device
         on_dev = all(i.is_cuda for i in images)
         raw = torch.zeros(len(images), 3, H, W, dtype=torch.float32, device=dev if on_dev else "cpu",
@@ -300,12 +314,16 @@ class CATSeg(nn.Module):
 
     def _labels(self, logits: torch.Tensor, hw, crop) -> List[dict]:
         """OUTPUT "labels": one catseg_postprocess_argmax launch for the images of `logits`, into fresh
-        tensors; each result holds views of them."""
+        tensors; each image's result (_label_result) holds views of them."""
         n, dev = logits.shape[0], logits.device
         labels = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.int32)
         score = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.float32)
         ops.postprocess_argmax(logits, labels, score, crop=crop)
-        return [{"sem_seg_labels": labels[i], "sem_seg_score": score[i]} for i in range(n)]
+        return [self._label_result(labels[i], score[i]) for i in range(n)]
+
+    def _label_result(self, labels: torch.Tensor, score: torch.Tensor) -> dict:
+        """One image's OUTPUT "labels" result, whichever branch made the map: with its regions (add_regions)."""
+        return self.add_regions({"sem_seg_labels": labels, "sem_seg_score": score})
 
     def add_regions(self, result: dict) -> dict:
         """MODEL.CATSEG_HIP.REGIONS: one image's {"sem_seg_labels", "sem_seg_score"} turned into objects, after
@@ -343,10 +361,7 @@ class CATSeg(nn.Module):
         handle = self._op_handle
         n_classes, res = custom_ops.head_meta(handle)
         images = [x["image"] for x in batched_inputs]
-        d = max(self.size_divisibility, 1)
-        H = max(int(i.shape[-2]) for i in images)
-        W = max(int(i.shape[-1]) for i in images)
-        H, W = -(-H // d) * d, -(-W // d) * d
+        H, W = self._canvas_geometry(images)
         dev = self._engine_device()
         raw = torch.zeros(len(images), 3, H, W, dtype=torch.float32, device=dev)
         for k, im in enumerate(images):
@@ -354,17 +369,14 @@ class CATSeg(nn.Module):
         sizes = [(int(i.shape[-2]), int(i.shape[-1])) for i in images]
         sizes_dev = torch.tensor(sizes, dtype=torch.int32, device=dev)
         logits = torch.ops.catseg.head_logits(raw, sizes_dev, handle, n_classes, res)
-        n = len(batched_inputs) if self.return_all_images else 1
         results = []
-        for i in range(n):
-            ih, iw = sizes[i]
-            h = int(batched_inputs[i].get("height", ih))
-            w = int(batched_inputs[i].get("width", iw))
+        plan = output_plan(batched_inputs, sizes, (res, res), self.return_all_images)
+        for i, ((h, w), (crop_h, crop_w)) in enumerate(plan):
             if self.output == "labels":
-                lab, sc = torch.ops.catseg.postprocess_argmax(logits[i:i + 1], h, w, min(res, ih), min(res, iw), True)
-                results.append({"sem_seg_labels": lab[0], "sem_seg_score": sc[0]})
+                lab, sc = torch.ops.catseg.postprocess_argmax(logits[i:i + 1], h, w, crop_h, crop_w, True)
+                results.append(self._label_result(lab[0], sc[0]))
                 continue
-            out = torch.ops.catseg.postprocess(logits[i:i + 1], h, w, min(res, ih), min(res, iw))
+            out = torch.ops.catseg.postprocess(logits[i:i + 1], h, w, crop_h, crop_w)
             results.append({"sem_seg": out[0]})
         return results
 
@@ -404,6 +416,7 @@ class CATSeg(nn.Module):
         slot["done"].record(torch.cuda.current_stream(canvas.device))
 
     def _canvas_geometry(self, images: List[torch.Tensor]):
+        """(H, W) of the batch's canvas: the batch maximum, rounded up to size_divisibility."""
         d = max(self.size_divisibility, 1)
         H = max(int(i.shape[-2]) for i in images)
         W = max(int(i.shape[-1]) for i in images)
@@ -442,34 +455,39 @@ class CATSeg(nn.Module):
         g["graph"].replay()
         return g["logits"], sizes
 
-    def _forward_graph(self, eng: CatSegEngine, batched_inputs: List[dict]):
-        """The eval forward as one hipGraph replay per input geometry (what bench.py times), then the
-        resize of the captured logits into fresh output tensors."""
-        logits, sizes = self._graph_logits(eng, batched_inputs)
-        dev = eng.device
-        n = len(batched_inputs) if self.return_all_images else 1
-        outs = tuple((int(batched_inputs[i].get("height", sizes[i][0])), int(batched_inputs[i].get("width", sizes[i][1])))
-                     for i in range(n))
-        # the resize to each image's output size runs after the replay into FRESH tensors (the caller
-        # may keep the results across calls), as the eager path does
-        h_l, w_l = logits.shape[-2:]
-        if n > 1 and len(set(outs)) == 1 and len(set(sizes[:n])) == 1:
-            # one launch for the whole batch (the engine leg's form); each result is a view of it
-            if self.output == "labels":
-                return [self.add_regions(r) for r in
-                        self._labels(logits[:n], outs[0], (min(h_l, sizes[0][0]), min(w_l, sizes[0][1])))]
-            out = torch.empty(n, logits.shape[1], outs[0][0], outs[0][1], device=dev)
-            ops.postprocess(logits[:n], out, crop=(min(h_l, sizes[0][0]), min(w_l, sizes[0][1])))
-            return [{"sem_seg": out[i]} for i in range(n)]
+    def _eval_engine(self) -> CatSegEngine:
+        """The eval engine with the test class set's text embeddings set on it."""
+        eng = self.engine
+        self.sem_seg_head.predictor.get_text_embeds()
+        return eng
+
+    def _eval_logits(self, batched_inputs: List[dict]):
+        """(logits, image sizes) of the whole batch: one hipGraph replay per input geometry under
+        MODEL.CATSEG_HIP.GRAPH (what bench.py times; the captured buffer, valid until the next call),
+        else eager launches on a fresh canvas."""
+        eng = self._eval_engine()
+        if self.use_graph:
+            return self._graph_logits(eng, batched_inputs)
+        raw, sizes_dev, sizes = self._batch(eng, [x["image"] for x in batched_inputs])
+        return eng.head_logits(raw, sizes_dev), sizes
+
+    def _finish(self, logits: torch.Tensor, sizes, plan) -> List[dict]:
+        """The output stage of the graph and the eager branch: the resize of `logits` by output_plan's
+        `plan` into FRESH tensors (on the graph branch it runs after the replay; the caller may keep the
+        results across calls).  A batch of more than one image whose image sizes and output sizes are all
+        equal takes one launch (the engine leg's form) and its results are views of that launch's tensor;
+        any other batch takes one launch per image."""
+        n = len(plan)
+        uniform = n > 1 and all(p == plan[0] for p in plan) and all(s == sizes[0] for s in sizes[:n])
         results = []
-        for i in range(n):
+        for lo, hi in [(0, n)] if uniform else [(i, i + 1) for i in range(n)]:
+            part, (hw, crop) = logits[lo:hi], plan[lo]
             if self.output == "labels":
-                results += [self.add_regions(r) for r in
-                            self._labels(logits[i:i + 1], outs[i], (min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))]
+                results += self._labels(part, hw, crop)
                 continue
-            out = torch.empty(1, logits.shape[1], outs[i][0], outs[i][1], device=dev)
-            ops.postprocess(logits[i:i + 1], out, crop=(min(h_l, sizes[i][0]), min(w_l, sizes[i][1])))
-            results.append({"sem_seg": out[0]})
+            out = torch.empty(part.shape[0], part.shape[1], hw[0], hw[1], device=logits.device)
+            ops.postprocess(part, out, crop=crop)
+            results += [{"sem_seg": o} for o in out]
         return results
 
     def forward_logits(self, batched_inputs: List[dict]):
@@ -490,15 +508,8 @@ class CATSeg(nn.Module):
         if torch.compiler.is_compiling():
             raise RuntimeError("CATSeg.forward_logits cannot be traced by torch.compile: call it eagerly")
         with torch.no_grad():
-            eng = self.engine
-            self.sem_seg_head.predictor.get_text_embeds()
-            if self.use_graph:
-                logits, sizes = self._graph_logits(eng, batched_inputs)
-            else:
-                raw, sizes_dev, sizes = self._batch(eng, [x["image"] for x in batched_inputs])
-                logits = eng.head_logits(raw, sizes_dev)
-            h_l, w_l = logits.shape[-2:]
-            return logits, [(min(h_l, ih), min(w_l, iw)) for ih, iw in sizes]
+            logits, sizes = self._eval_logits(batched_inputs)
+            return logits, [crop for _, crop in output_plan(batched_inputs, sizes, logits.shape[-2:], True)]
 
     def forward(self, batched_inputs: List[dict]):
         if self.training:
@@ -510,27 +521,9 @@ class CATSeg(nn.Module):
         if torch.compiler.is_compiling():
             return self._forward_traced(batched_inputs)
         with torch.no_grad():
-            eng = self.engine
-            self.sem_seg_head.predictor.get_text_embeds()
-            if self.use_graph:
-                return self._forward_graph(eng, batched_inputs)
-            raw, sizes_dev, sizes = self._batch(eng, [x["image"] for x in batched_inputs])
-            logits = eng.head_logits(raw, sizes_dev)
-            n = len(batched_inputs) if self.return_all_images else 1
-            results = []
-            h_l, w_l = logits.shape[-2:]
-            for i in range(n):
-                ih, iw = sizes[i]
-                h = int(batched_inputs[i].get("height", ih))
-                w = int(batched_inputs[i].get("width", iw))
-                if self.output == "labels":
-                    results += [self.add_regions(r) for r in
-                                self._labels(logits[i:i + 1], (h, w), (min(h_l, ih), min(w_l, iw)))]
-                    continue
-                out = torch.empty(1, logits.shape[1], h, w, device=eng.device)
-                ops.postprocess(logits[i:i + 1], out, crop=(min(h_l, ih), min(w_l, iw)))
-                results.append({"sem_seg": out[0]})
-            return results
+            logits, sizes = self._eval_logits(batched_inputs)
+            plan = output_plan(batched_inputs, sizes, logits.shape[-2:], self.return_all_images)
+            return self._finish(logits, sizes, plan)
 
     def _forward_tiled(self, batched_inputs: List[dict]):
         """MODEL.CATSEG_HIP.TILED eval: every image (or image 0 in the reference mode) at its own resolution
@@ -540,11 +533,9 @@ class CATSeg(nn.Module):
             raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.TILED cannot be traced by torch.compile: the "
                                "tile grid follows each image's size; call it eagerly")
         with torch.no_grad():
-            eng = self.engine
-            self.sem_seg_head.predictor.get_text_embeds()
-            n = len(batched_inputs) if self.return_all_images else 1
+            eng = self._eval_engine()
             results = []
-            for x in batched_inputs[:n]:
+            for x in returned_inputs(batched_inputs, self.return_all_images):
                 im = x["image"]
                 ih, iw = int(im.shape[-2]), int(im.shape[-1])
                 if (int(x.get("height", ih)), int(x.get("width", iw))) != (ih, iw):
@@ -557,7 +548,7 @@ class CATSeg(nn.Module):
                                         stride=self.tiled_stride, batch=self.tiled_batch,
                                         window=self.tiled_window, global_view=self.tiled_global)
                 if self.output == "labels":
-                    results.append(self.add_regions({"sem_seg_labels": out[0], "sem_seg_score": out[1]}))
+                    results.append(self._label_result(*out))
                 else:
                     results.append({"sem_seg": out})
             return results
@@ -608,15 +599,13 @@ class CATSeg(nn.Module):
         """TEST.SLIDING_WINDOW eval (cat_seg_model.py:156-176,204-218): every image (or image 0 in
         the reference mode) through 4 Unfold tiles + 1 global crop; height/width default to 640."""
         with torch.no_grad():
-            eng = self.engine
-            self.sem_seg_head.predictor.get_text_embeds()
-            n = len(batched_inputs) if self.return_all_images else 1
-            inputs = batched_inputs[:n]
+            eng = self._eval_engine()
+            inputs = returned_inputs(batched_inputs, self.return_all_images)
             raw, sizes_dev, _ = self._batch(eng, [x["image"] for x in inputs])
             res = eng.SLIDE_OUT
             out_hw = [(int(x.get("height", res)), int(x.get("width", res))) for x in inputs]
             if self.output == "labels":
-                return [self.add_regions({"sem_seg_labels": lab, "sem_seg_score": sc})
+                return [self._label_result(lab, sc)
                         for lab, sc in eng.forward_sliding(raw, sizes_dev, out_hw, labels=True)]
             return [{"sem_seg": o} for o in eng.forward_sliding(raw, sizes_dev, out_hw)]
 

@@ -765,19 +765,6 @@ class CatSegEngine:
                                  T_out=T0, classes=classes, gn=(m2, r2, *dec.g3, 16))
         return logits
 
-    # ------------------------------------------------------------------ full eval forward
-    def forward(self, raw: torch.Tensor, sizes: torch.Tensor, out_hw, image_hw) -> torch.Tensor:
-        """Sigmoid probabilities upsampled to out_hw for every image (cat_seg_model.py:220-229).
-        image_hw: the host-side (h, w) of the valid image region, which sem_seg_postprocess crops
-        to (one size for the whole batch; CATSeg.forward handles ragged batches per image)."""
-        logits = self.head_logits(raw, sizes)
-        B, T0, h, w = logits.shape
-        H, W = out_hw
-        out = torch.empty(B, T0, H, W, device=self.device, dtype=_f32)
-        ih, iw = (int(v) for v in image_hw)
-        ops.postprocess(logits, out, crop=(min(h, ih), min(w, iw)))
-        return out
-
     # ------------------------------------------------------------------ tiled eval at native resolution
     def forward_tiled(self, image: torch.Tensor, labels: bool = False, *, tile: int = 384, stride: int = 256,
                       batch: int = 8, window: str = "uniform", global_view: bool = False):

@@ -109,6 +109,31 @@ def test_forward_fails_loudly_without_gpu():
         m([{"image": torch.zeros(3, 64, 64)}])
 
 
+def test_output_plan_sizes_and_crops():
+    """cat_seg_model.output_plan, the one statement of what the output stage does per image: how many results,
+    each result's size ("height" / "width", each defaulting to the image's own) and the crop of the logits
+    (here 96 x 96) that the resize reads."""
+    from cat_seg.cat_seg_model import output_plan
+    a, b, c = torch.zeros(3, 384, 384), torch.zeros(3, 300, 352), torch.zeros(3, 40, 48)
+
+    def sizes(*ims):
+        return [tuple(i.shape[-2:]) for i in ims]
+
+    inputs = [{"image": a, "height": 200, "width": 300}, {"image": b}]
+    assert output_plan(inputs, sizes(a, b), (96, 96), True) == [((200, 300), (96, 96)), ((300, 352), (96, 96))]
+    # an image below the logits' resolution: the crop is the image's own size
+    assert output_plan([{"image": c}], sizes(c), (96, 96), True) == [((40, 48), (40, 48))]
+    # only "height" given: "width" is the image's own
+    assert output_plan([{"image": b, "height": 200}], sizes(b), (96, 96), True) == [((200, 352), (96, 96))]
+    assert output_plan([{"image": c, "width": 50}], sizes(c), (96, 96), True) == [((40, 50), (40, 48))]
+    # the reference mode: one entry, for image 0
+    assert output_plan(inputs, sizes(a, b), (96, 96), False) == [((200, 300), (96, 96))]
+    # ints and tuples only (what lets dynamo trace through it), whatever the sizes came as
+    plan = output_plan(inputs, [[384, 384], [300, 352]], torch.Size((96, 96)), True)
+    assert plan == [((200, 300), (96, 96)), ((300, 352), (96, 96))]
+    assert all(type(v) is int for hw, crop in plan for v in (*hw, *crop))
+
+
 def test_capi_library_exports_every_header_symbol():
     hdr = open(os.path.join(ROOT, "include", "catseg_hip.h")).read()
     declared = set(re.findall(r"\b(catseg_[a-z0-9_]+)\s*\(", hdr))

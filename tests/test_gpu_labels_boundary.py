@@ -29,13 +29,15 @@ def _tokens(name="e2e_tiny_eval"):
     return _TOKENS[name]
 
 
+def _model(output, **over):
+    m = build_model(tiny_cfg(**{"MODEL.CATSEG_HIP.OUTPUT": output, **over})).cuda().eval()
+    m.sem_seg_head.predictor.set_class_tokens(_tokens()["tokens"])
+    return m
+
+
 def _pair(**over):
     """The tiny model twice with the same (seed 0) weights: OUTPUT "probs" and "labels"."""
-    models = []
-    for output in ("probs", "labels"):
-        m = build_model(tiny_cfg(**{"MODEL.CATSEG_HIP.OUTPUT": output, **over})).cuda().eval()
-        m.sem_seg_head.predictor.set_class_tokens(_tokens()["tokens"])
-        models.append(m)
+    models = [_model(output, **over) for output in ("probs", "labels")]
     assert models[0].output == "probs" and models[1].output == "labels"
     return models
 
@@ -80,13 +82,49 @@ def test_labels_equal_argmax_of_probs(graph):
     assert lr[0]["sem_seg_labels"].shape == (200, 300) and lr[1]["sem_seg_labels"].shape == (300, 352)
     for p, l in zip(pr, lr):
         _assert_exact(p, l)
-    # equal sizes: the graph branch resizes the whole batch with one launch
+    # equal sizes: the whole batch is resized with one launch
     c, d = _images([(3, 300, 352)] * 2, seed=4)
     inputs = [{"image": c}, {"image": d}]
     pr, lr = pm(inputs), lm(inputs)
     for p, l in zip(pr, lr):
         _assert_exact(p, l)
     assert not torch.equal(lr[0]["sem_seg_labels"], lr[1]["sem_seg_labels"])
+
+
+def _assert_same_result(got, want):
+    assert got.keys() == want.keys()
+    for k in got:
+        if k == "regions_info":
+            assert got[k].keys() == want[k].keys()
+            for col in got[k]:
+                assert torch.equal(got[k][col], want[k][col]), (k, col)
+        else:
+            assert torch.equal(got[k], want[k]), k
+
+
+@pytest.mark.parametrize("output", ["probs", "labels"])
+def test_eager_batch_equals_single_image_calls(output):
+    """MODEL.CATSEG_HIP.GRAPH False: a uniform batch (equal image sizes, equal output sizes) is resized with one
+    launch, its results views of one tensor, and a batch with one output size changed with one launch per
+    image; either way every returned tensor equals what a call with that image alone returns (the labels
+    model with its regions: the region numbers and every column of the table)."""
+    over = {"MODEL.CATSEG_HIP.GRAPH": "False"}
+    if output == "labels":
+        over["MODEL.CATSEG_HIP.REGIONS.ENABLED"] = "True"
+    m = _model(output, **over)
+    assert not m.use_graph
+    key = "sem_seg" if output == "probs" else "sem_seg_score"
+    ims =_images([(3, 40, 48)] * 3)
+    asked = {"height": 50, "width": 60}
+    for sizes, uniform in (([{}] * 3, True), ([asked] * 3, True), ([asked, {**asked, "height": 44}, asked], False)):
+        inputs = [{"image": im, **s} for im, s in zip(ims, sizes)]
+        batch = m(inputs)
+        assert len(batch) == 3
+        for x, got in zip(inputs, batch):
+            assert got[key].shape[-2:] == (x.get("height", 40), x.get("width", 48))
+            assert got[key]._base.shape[0] == (3 if uniform else 1)      # the launch this result is a view of
+            _assert_same_result(got, m([x])[0])
+        assert not torch.equal(batch[0][key], batch[2][key])
 
 
 def test_odd_output_width_is_within_rounding():
