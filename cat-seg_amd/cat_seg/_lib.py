@@ -24,6 +24,8 @@ TUNING_HEADER = "catseg_hip_tuning.h"          # diagnostics entry, not part of 
 INCLUDED_HEADERS = ("catseg_hip_simplify.h",)
 # later function-only headers catseg_hip.h includes, a group of their own (the boundary-aware evaluation)
 EXTENSION_HEADERS = ("catseg_hip_boundary.h",)
+# and a third such group (the label-map renderer)
+RENDER_HEADERS = ("catseg_hip_render.h",)
 
 BIG = 1 << 62
 
@@ -150,6 +152,11 @@ _EXTENSION_PROTOS = _read_included_headers(_STRUCTS, EXTENSION_HEADERS)
 if set(_EXTENSION_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS)):
     raise RuntimeError(f"declared twice: {sorted(set(_EXTENSION_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS)))}")
 EXPORTED_EXTENSIONS = tuple(_EXTENSION_PROTOS)
+_RENDER_PROTOS = _read_included_headers(_STRUCTS, RENDER_HEADERS)
+if set(_RENDER_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS) | set(_EXTENSION_PROTOS)):
+    raise RuntimeError("declared twice: "
+                       f"{sorted(set(_RENDER_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS) | set(_EXTENSION_PROTOS)))}")
+EXPORTED_RENDER = tuple(_RENDER_PROTOS)
 # the struct classes under their header names without the prefix: RowMap, GemmArgs, RowsEpi, AdamWTensor, ...
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})
 F32, BF16, FP8 = (_ENUMS["CATSEG_" + n] for n in ("F32", "BF16", "FP8"))
@@ -176,7 +183,7 @@ def load() -> C.CDLL:
             f"libcatseg_hip.so not found at {LIB_PATH}: build it with "
             "`make -C cat-seg_amd/csrc` (or __graft_entry__.build()); the CAT-Seg HIP path has no fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS, **_EXTENSION_PROTOS}.items():
+    for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS, **_EXTENSION_PROTOS, **_RENDER_PROTOS}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

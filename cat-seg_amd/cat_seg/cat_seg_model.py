@@ -19,6 +19,8 @@ With MODEL.CATSEG_HIP.REGIONS.ENABLED (OUTPUT "labels") every returned label map
 described by "sem_seg_regions" + "regions_info" on the device (CATSeg.add_regions; ops.label_regions), with
 REGIONS.OUTLINES by "regions_outlines", the regions' boundaries as polygon rings (ops.region_outlines), and with
 REGIONS.SIMPLIFY.ENABLED by "regions_outlines_simplified", those rings simplified arc by arc (ops.simplify_outlines).
+With MODEL.CATSEG_HIP.RENDER.ENABLED (OUTPUT "labels") every returned dict gains "sem_seg_render", the final label
+map as an RGB picture over its own input image (CATSeg.add_render; ops.render_labels).
 
 Everything between the input copy and the returned tensors runs in the HIP kernels of
 libcatseg_hip.so through `CatSegEngine`; there is no CPU or PyTorch-op fallback.
@@ -95,7 +97,9 @@ class CATSeg(nn.Module):
                  tiled_tile: int = 384, tiled_stride: int = 256, tiled_batch: int = 8, tta_merge: str = "host",
                  tiled_window: str = "uniform", tiled_global: bool = False, regions: bool = False,
                  regions_connectivity: int = 8, regions_min_area: int = 0, regions_outlines: bool = False,
-                 regions_simplify: bool = False, regions_simplify_tolerance: float = 1.0):
+                 regions_simplify: bool = False, regions_simplify_tolerance: float = 1.0, render: bool = False,
+                 render_alpha: float = 0.5, render_gray: bool = True, render_edge_px: int = 1, render_factor: int = 1,
+                 render_score_alpha: bool = False, render_palette: str = ""):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
@@ -123,6 +127,19 @@ class CATSeg(nn.Module):
         if self.regions_simplify and not 0.0 <= self.regions_simplify_tolerance <= ops.SIMPLIFY_MAX_SIDE:
             raise ValueError("CATSeg: MODEL.CATSEG_HIP.REGIONS.SIMPLIFY.TOLERANCE must be in "
                              f"[0, {ops.SIMPLIFY_MAX_SIDE}] pixels, got {regions_simplify_tolerance!r}")
+        # the returned label map as an RGB picture (MODEL.CATSEG_HIP.RENDER; ops.render_labels)
+        self.render = bool(render)
+        self.render_alpha, self.render_gray = float(render_alpha), bool(render_gray)
+        self.render_edge_px, self.render_factor = int(render_edge_px), int(render_factor)
+        self.render_score_alpha, self.render_palette = bool(render_score_alpha), str(render_palette)
+        self._render_palettes: Dict[tuple, torch.Tensor] = {}
+        if self.render and output != "labels":
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.RENDER draws the label map of "
+                             f"MODEL.CATSEG_HIP.OUTPUT 'labels', not {output!r}")
+        if self.render and not (0.0 <= self.render_alpha <= 1.0 and 0 <= self.render_edge_px <= 8
+                                and 1 <= self.render_factor <= 64):
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.RENDER needs ALPHA in [0, 1], EDGE_PX in 0 .. 8 and FACTOR in "
+                             f"1 .. 64, got {render_alpha!r}, {render_edge_px!r}, {render_factor!r}")
         # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
         self.tiled = bool(tiled)
         self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
@@ -182,6 +199,7 @@ class CATSeg(nn.Module):
         hip = cfg.MODEL.get("CATSEG_HIP", {}) if hasattr(cfg.MODEL, "get") else {}
         tiled = (hip.get("TILED", None) if hip else None) or {}
         regions = (hip.get("REGIONS", None) if hip else None) or {}
+        render = (hip.get("RENDER", None) if hip else None) or {}
         return {
             "backbone": None,
             "sem_seg_head": build_sem_seg_head(cfg, None),
@@ -216,6 +234,13 @@ class CATSeg(nn.Module):
             "regions_outlines": bool(regions.get("OUTLINES", False)),
             "regions_simplify": bool((regions.get("SIMPLIFY", None) or {}).get("ENABLED", False)),
             "regions_simplify_tolerance": float((regions.get("SIMPLIFY", None) or {}).get("TOLERANCE", 1.0)),
+            "render": bool(render.get("ENABLED", False)),
+            "render_alpha": float(render.get("ALPHA", 0.5)),
+            "render_gray": bool(render.get("GRAY", True)),
+            "render_edge_px": int(render.get("EDGE_PX", 1)),
+            "render_factor": int(render.get("FACTOR", 1)),
+            "render_score_alpha": bool(render.get("SCORE_ALPHA", False)),
+            "render_palette": str(render.get("PALETTE", "")),
         }
 
     # ------------------------------------------------------------------ parameters
@@ -312,20 +337,52 @@ class CATSeg(nn.Module):
         sizes_dev = torch.tensor(sizes, dtype=torch.int32).to(dev, non_blocking=True)
         return (raw if on_dev else raw.to(dev, non_blocking=True)), sizes_dev, sizes
 
-    def _labels(self, logits: torch.Tensor, hw, crop) -> List[dict]:
+    def _labels(self, logits: torch.Tensor, hw, crop, images=None) -> List[dict]:
         """OUTPUT "labels": one catseg_postprocess_argmax launch for the images of `logits`, into fresh
-        tensors; each image's result (_label_result) holds views of them."""
+        tensors; each image's result (_label_result) holds views of them.  `images`: the input images of
+        `logits`, which MODEL.CATSEG_HIP.RENDER draws over."""
         n, dev = logits.shape[0], logits.device
         labels = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.int32)
         score = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.float32)
         ops.postprocess_argmax(logits, labels, score, crop=crop)
-        return [self._label_result(labels[i], score[i]) for i in range(n)]
+        return [self._label_result(labels[i], score[i], None if images is None else images[i]) for i in range(n)]
 
-    def _label_result(self, labels: torch.Tensor, score: torch.Tensor) -> dict:
-        """One image's OUTPUT "labels" result, whichever branch made the map: with its regions (add_regions)."""
-        return self.add_regions({"sem_seg_labels": labels, "sem_seg_score": score})
+    def _label_result(self, labels: torch.Tensor, score: torch.Tensor, image=None) -> dict:
+        """One image's OUTPUT "labels" result, whichever branch made the map: with its regions (add_regions) and,
+        over `image`, its picture (add_render)."""
+        return self.add_regions({"sem_seg_labels": labels, "sem_seg_score": score}, image)
 
-    def add_regions(self, result: dict) -> dict:
+    def _palette(self, device) -> torch.Tensor:
+        """The (P, 3) uint8 palette of MODEL.CATSEG_HIP.RENDER on `device`: RENDER.PALETTE's catalog colours, or
+        the colour map over the test classes; made once per class count."""
+        n = int(self.sem_seg_head.predictor.class_tokens("test").shape[0])
+        key = (n, str(device))
+        if key not in self._render_palettes:
+            from .visualize import palette_for
+            self._render_palettes[key] = palette_for(self.render_palette or None, n, device=device)
+        return self._render_palettes[key]
+
+    def add_render(self, result: dict, image) -> dict:
+        """MODEL.CATSEG_HIP.RENDER: one image's result with "sem_seg_render", (ceil(h / FACTOR), ceil(w / FACTOR), 3)
+        uint8 on the device: ops.render_labels of the final "sem_seg_labels" (after the sieve of REGIONS.MIN_AREA)
+        over `image`, the dict's own (3, H, W) input image, sampled to the map's size by the nearest pixel centre;
+        ALPHA, GRAY, EDGE_PX and FACTOR as configured, SCORE_ALPHA fading the colours by "sem_seg_score".  A float
+        image is clamped to 0 .. 255 and truncated to uint8.  One launch after the graph replay or the merge,
+        outside any captured graph.  A no-op with RENDER.ENABLED False."""
+        if not self.render:
+            return result
+        labels = result["sem_seg_labels"]
+        if image is None:
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.RENDER draws over the input image, which this call has none of")
+        image = image.to(labels.device)
+        if image.dtype != torch.uint8:
+            image = image.clamp(0, 255).to(torch.uint8)
+        picture = ops.render_labels(labels, self._palette(labels.device), image=image, gray=self.render_gray,
+                                    alpha=self.render_alpha, edge_px=self.render_edge_px, factor=self.render_factor,
+                                    score=result["sem_seg_score"] if self.render_score_alpha else None)
+        return {**result, "sem_seg_render": picture}
+
+    def add_regions(self, result: dict, image=None) -> dict:
         """MODEL.CATSEG_HIP.REGIONS: one image's {"sem_seg_labels", "sem_seg_score"} turned into objects, after
         the graph replay or the merge and outside any captured graph (the table's size depends on the data: one
         4-byte read of R).  MIN_AREA > 1 replaces "sem_seg_labels" by its sieve ("sem_seg_score" stays as it is);
@@ -335,9 +392,10 @@ class CATSeg(nn.Module):
         number, every region has one exterior ring, and they come in region order.  With REGIONS.SIMPLIFY.ENABLED,
         "regions_outlines_simplified" = ops.simplify_outlines of those rings under SIMPLIFY.TOLERANCE (two more
         4-byte reads: nodes, kept vertices); "regions_outlines" stays as it is.  A no-op with REGIONS.ENABLED
-        False."""
+        False.  The junction every branch that returns labels passes: with `image` the result goes on through
+        add_render (MODEL.CATSEG_HIP.RENDER), drawn from the final map."""
         if not self.regions:
-            return result
+            return self.add_render(result, image)
         labels, conn = result["sem_seg_labels"], self.regions_connectivity
         if self.regions_min_area > 1:
             labels = ops.sieve_labels(labels, self.regions_min_area, connectivity=conn)
@@ -349,7 +407,7 @@ class CATSeg(nn.Module):
             if self.regions_simplify:
                 out["regions_outlines_simplified"] = ops.simplify_outlines(ids, out["regions_outlines"],
                                                                            self.regions_simplify_tolerance)
-        return out
+        return self.add_render(out, image)
 
     def _forward_traced(self, batched_inputs: List[dict]):
         """The eval forward as dynamo traces it (torch.compile): the canvas staging in torch ops, the
@@ -358,6 +416,9 @@ class CATSeg(nn.Module):
         if self.regions:
             raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.REGIONS cannot be traced by torch.compile: the "
                                "region table's size depends on the data; call it eagerly")
+        if self.render:
+            raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.RENDER cannot be traced by torch.compile: the "
+                               "picture is drawn by a launch outside the registered operators; call it eagerly")
         handle = self._op_handle
         n_classes, res = custom_ops.head_meta(handle)
         images = [x["image"] for x in batched_inputs]
@@ -471,7 +532,7 @@ class CATSeg(nn.Module):
         raw, sizes_dev, sizes = self._batch(eng, [x["image"] for x in batched_inputs])
         return eng.head_logits(raw, sizes_dev), sizes
 
-    def _finish(self, logits: torch.Tensor, sizes, plan) -> List[dict]:
+    def _finish(self, logits: torch.Tensor, sizes, plan, images=None) -> List[dict]:
         """The output stage of the graph and the eager branch: the resize of `logits` by output_plan's
         `plan` into FRESH tensors (on the graph branch it runs after the replay; the caller may keep the
         results across calls).  A batch of more than one image whose image sizes and output sizes are all
@@ -483,7 +544,7 @@ class CATSeg(nn.Module):
         for lo, hi in [(0, n)] if uniform else [(i, i + 1) for i in range(n)]:
             part, (hw, crop) = logits[lo:hi], plan[lo]
             if self.output == "labels":
-                results += self._labels(part, hw, crop)
+                results += self._labels(part, hw, crop, None if images is None else images[lo:hi])
                 continue
             out = torch.empty(part.shape[0], part.shape[1], hw[0], hw[1], device=logits.device)
             ops.postprocess(part, out, crop=crop)
@@ -523,7 +584,7 @@ class CATSeg(nn.Module):
         with torch.no_grad():
             logits, sizes = self._eval_logits(batched_inputs)
             plan = output_plan(batched_inputs, sizes, logits.shape[-2:], self.return_all_images)
-            return self._finish(logits, sizes, plan)
+            return self._finish(logits, sizes, plan, [x["image"] for x in batched_inputs])
 
     def _forward_tiled(self, batched_inputs: List[dict]):
         """MODEL.CATSEG_HIP.TILED eval: every image (or image 0 in the reference mode) at its own resolution
@@ -548,7 +609,7 @@ class CATSeg(nn.Module):
                                         stride=self.tiled_stride, batch=self.tiled_batch,
                                         window=self.tiled_window, global_view=self.tiled_global)
                 if self.output == "labels":
-                    results.append(self._label_result(*out))
+                    results.append(self._label_result(*out, im))
                 else:
                     results.append({"sem_seg": out})
             return results
@@ -605,8 +666,8 @@ class CATSeg(nn.Module):
             res = eng.SLIDE_OUT
             out_hw = [(int(x.get("height", res)), int(x.get("width", res))) for x in inputs]
             if self.output == "labels":
-                return [self._label_result(lab, sc)
-                        for lab, sc in eng.forward_sliding(raw, sizes_dev, out_hw, labels=True)]
+                return [self._label_result(lab, sc, x["image"])
+                        for x, (lab, sc) in zip(inputs, eng.forward_sliding(raw, sizes_dev, out_hw, labels=True))]
             return [{"sem_seg": o} for o in eng.forward_sliding(raw, sizes_dev, out_hw)]
 
 

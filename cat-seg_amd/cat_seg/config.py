@@ -233,4 +233,18 @@ def add_cat_seg_config(cfg):
     cfg.MODEL.CATSEG_HIP.REGIONS.SIMPLIFY = C()
     cfg.MODEL.CATSEG_HIP.REGIONS.SIMPLIFY.ENABLED = False
     cfg.MODEL.CATSEG_HIP.REGIONS.SIMPLIFY.TOLERANCE = 1.0
+    # OUTPUT "labels" only: every returned dict gains "sem_seg_render", its final label map as an RGB picture
+    # ((ceil(h / FACTOR), ceil(w / FACTOR), 3) uint8 on the device; CATSeg.add_render, ops.render_labels): the palette
+    # colours blended at ALPHA over the dict's own input image (GRAY: over its luma), label edges EDGE_PX (0 .. 8)
+    # wide in white, reduced by FACTOR (1 .. 64; 8 makes a quicklook), SCORE_ALPHA fading the colours by
+    # "sem_seg_score".  PALETTE: a catalog name whose stuff_colors to use; "" = the PASCAL VOC colour map over the
+    # test classes
+    cfg.MODEL.CATSEG_HIP.RENDER = C()
+    cfg.MODEL.CATSEG_HIP.RENDER.ENABLED = False
+    cfg.MODEL.CATSEG_HIP.RENDER.ALPHA = 0.5
+    cfg.MODEL.CATSEG_HIP.RENDER.GRAY = True
+    cfg.MODEL.CATSEG_HIP.RENDER.EDGE_PX = 1
+    cfg.MODEL.CATSEG_HIP.RENDER.FACTOR = 1
+    cfg.MODEL.CATSEG_HIP.RENDER.SCORE_ALPHA = False
+    cfg.MODEL.CATSEG_HIP.RENDER.PALETTE = ""
     return cfg

@@ -957,6 +957,105 @@ def boundary_confusion(pred, gt, widths, counters, *, num_classes, ignore_label=
     return counters
 
 
+def _rgb24(v, what):
+    """(r, g, b) in 0 .. 255 or a packed 0xRRGGBB int -> the packed int."""
+    if isinstance(v, int) and not isinstance(v, bool):
+        if not 0 <= v <= 0xFFFFFF:
+            raise ValueError(f"{what} must lie in 0x000000 .. 0xFFFFFF, got {v:#x}")
+        return v
+    try:
+        r, g, b = (int(c) for c in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be (r, g, b) or a packed 0xRRGGBB int, got {v!r}") from None
+    if not all(0 <= c <= 255 for c in (r, g, b)):
+        raise ValueError(f"{what} must hold values in 0 .. 255, got {v!r}")
+    return (r << 16) | (g << 8) | b
+
+
+def _render_side_map(t, name, dtype, H, W, device):
+    """ld of an optional (H, W) map of `dtype` beside the labels of render_labels."""
+    what = "render_labels"
+    if not torch.is_tensor(t) or t.device != device:
+        raise ValueError(f"{what}: {name} must be a tensor on the labels' device")
+    if t.dtype != dtype or tuple(t.shape) != (H, W):
+        raise ValueError(f"{what}: {name} must be an ({H}, {W}) {dtype} tensor, got {t.dtype} {tuple(t.shape)}")
+    if W > 1 and t.stride(1) != 1:
+        raise ValueError(f"{what}: the rows of {name} must be contiguous (stride {t.stride(1)})")
+    ld = t.stride(0) if H > 1 else W
+    if ld < W:
+        raise ValueError(f"{what}: row stride {ld} of {name} < W = {W}")
+    return ld
+
+
+def render_labels(labels, palette, *, image=None, gray=True, alpha=0.5, score=None, gt=None, ignore_label=255,
+                  error_rgb=(255, 0, 0), ignore_rgb=(0, 0, 0), edge_px=0, edge_rgb=(255, 255, 255), factor=1,
+                  other_rgb=(0, 0, 0), clamp_pred=-1, out=None):
+    """A label map as an RGB picture on the device (catseg_render_labels; DESIGN.md section 4, "Rendering"):
+    (ceil(H / factor), ceil(W / factor), 3) uint8.  Per pixel the palette colour of its label (other_rgb outside the
+    palette), with `gt` ignore_rgb where gt == ignore_label and error_rgb where gt differs, blended over `image`
+    at `alpha` (times the score, with `score`), edge_rgb where another label lies within edge_px; then the rounded
+    mean over factor x factor cells.  Integer arithmetic, bit-exact against tests/render_ref.py.
+      labels  2-D int32 CUDA map, rows may be strided; labels >= clamp_pred fold to clamp_pred (< 0: no fold)
+      palette (P, 3) uint8 on the same device, 1 <= P <= 8192
+      image   uint8, (3, ih, iw) or (ih, iw, 3) (a first dimension of 3 reads as channels), any strides, any size:
+              sampled to H x W by the nearest pixel centre; gray: use its luma (PIL's "L") as the background
+      score   (H, W) float32, gt (H, W) int32: rows may be strided
+      alpha   0 .. 1, used as round(256 alpha); edge_px 0 .. 8; factor 1 .. 64; colours (r, g, b) or 0xRRGGBB
+      out     (Ho, Wo, 3) uint8 whose pixels are contiguous, rows may be strided (fresh when None)
+    Returns out.  One launch, no workspace, no host synchronisation."""
+    what = "render_labels"
+    H, W, ld = _label_map_args(labels, what)
+    dev = labels.device
+    if H > 16384 or W > 16384:
+        raise ValueError(f"{what}: H and W must lie in 1 .. 16384, got {H} x {W}")
+    if (not torch.is_tensor(palette) or palette.device != dev or palette.dtype != torch.uint8 or palette.dim() != 2
+            or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 8192 or not palette.is_contiguous()):
+        raise ValueError(f"{what}: palette must be a contiguous (P, 3) uint8 tensor on the labels' device, "
+                         "1 <= P <= 8192")
+    try:
+        alpha_q8 = int(round(256 * float(alpha)))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: alpha must be a number in 0 .. 1, got {alpha!r}") from None
+    if not 0 <= alpha_q8 <= 256:
+        raise ValueError(f"{what}: alpha must lie in 0 .. 1, got {alpha!r}")
+    if not isinstance(edge_px, int) or isinstance(edge_px, bool) or not 0 <= edge_px <= 8:
+        raise ValueError(f"{what}: edge_px must be an int in 0 .. 8, got {edge_px!r}")
+    if not isinstance(factor, int) or isinstance(factor, bool) or not 1 <= factor <= 64:
+        raise ValueError(f"{what}: factor must be an int in 1 .. 64, got {factor!r}")
+    colours = [_rgb24(v, f"{what}: {n}") for n, v in (("other_rgb", other_rgb), ("error_rgb", error_rgb),
+                                                      ("ignore_rgb", ignore_rgb), ("edge_rgb", edge_rgb))]
+    img_args = (None, 0, 0, 0, 0, 0)
+    if image is not None:
+        if (not torch.is_tensor(image) or image.device != dev or image.dtype != torch.uint8 or image.dim() != 3
+                or image.numel() == 0 or 3 not in (image.shape[0], image.shape[2])):
+            raise ValueError(f"{what}: image must be a (3, h, w) or (h, w, 3) uint8 tensor on the labels' device")
+        sc, sr, sx = image.stride() if image.shape[0] == 3 else (image.stride(2), image.stride(0), image.stride(1))
+        ih, iw = image.shape[1:] if image.shape[0] == 3 else image.shape[:2]
+        if ih > 16384 or iw > 16384:
+            raise ValueError(f"{what}: image sides must lie in 1 .. 16384, got {ih} x {iw}")
+        img_args = (image.data_ptr(), ih, iw, sr, sx, sc)
+    ld_score = 0 if score is None else _render_side_map(score, "score", torch.float32, H, W, dev)
+    ld_gt = 0 if gt is None else _render_side_map(gt, "gt", torch.int32, H, W, dev)
+    Ho, Wo = -(-H // factor), -(-W // factor)
+    if out is None:
+        out = torch.empty((Ho, Wo, 3), dtype=torch.uint8, device=dev)
+    if (not torch.is_tensor(out) or out.device != dev or out.dtype != torch.uint8 or tuple(out.shape) != (Ho, Wo, 3)
+            or out.stride(2) != 1 or (Wo > 1 and out.stride(1) != 3)):
+        raise ValueError(f"{what}: out must be an ({Ho}, {Wo}, 3) uint8 tensor on the labels' device whose pixels are "
+                         "contiguous")
+    ld_out = out.stride(0) if Ho > 1 else 3 * Wo
+    if ld_out < 3 * Wo:
+        raise ValueError(f"{what}: row stride {ld_out} of out < 3 Wo = {3 * Wo}")
+    nbytes = H * W * (4 + (3 if image is not None else 0) + (4 if score is not None else 0)
+                      + (4 if gt is not None else 0)) + 3 * Ho * Wo
+    with _rec("render_labels", 0, nbytes):
+        call("catseg_render_labels", labels.data_ptr(), H, W, ld, int(clamp_pred), palette.data_ptr(),
+             palette.shape[0], colours[0], *img_args, int(bool(gray)), _p(score), ld_score, _p(gt), ld_gt,
+             int(ignore_label), colours[1], colours[2], alpha_q8, edge_px, colours[3], factor, out.data_ptr(), ld_out,
+             _stream())
+    return out
+
+
 def label_runs_count(labels, *, clamp_pred=-1):
     """Count + scan half of `label_runs` (catseg_label_runs_count): returns the int32 workspace tensor, whose
     element 0 is the number of runs R (still on the device) and whose rest holds the write offsets."""

@@ -80,7 +80,8 @@ class SemanticSegmentorWithTTA(_tta.SemanticSegmentorWithTTA):
             ops.postprocess_tta(buf, views, labels=labels, score=score)
             result = {"sem_seg_labels": labels, "sem_seg_score": score}
             add_regions = getattr(self.model, "add_regions", None)     # MODEL.CATSEG_HIP.REGIONS, on the merged map
-            return add_regions(result) if add_regions is not None else result
+            # (and MODEL.CATSEG_HIP.RENDER, over the image the views were made from)
+            return add_regions(result, inp.get("image")) if add_regions is not None else result
         probs = torch.empty(buf.shape[1], height, width, device=dev, dtype=torch.float32)
         ops.postprocess_tta(buf, views, probs=probs)
         return {"sem_seg": probs}

@@ -715,5 +715,7 @@ int catseg_region_outlines_write(const int32_t* ids, int64_t H, int64_t W, int64
 #include "catseg_hip_simplify.h"
 /* catseg_boundary_*: boundary distance of a label map and the counters of the boundary-aware metrics */
 #include "catseg_hip_boundary.h"
+/* catseg_render_labels: a label map as an RGB picture (overlay, edges, error map, quicklook) */
+#include "catseg_hip_render.h"
 
 #endif /* CATSEG_HIP_H */
