@@ -26,6 +26,8 @@ INCLUDED_HEADERS = ("catseg_hip_simplify.h",)
 EXTENSION_HEADERS = ("catseg_hip_boundary.h",)
 # and a third such group (the label-map renderer)
 RENDER_HEADERS = ("catseg_hip_render.h",)
+# and a fourth (the confidence outputs: top-k label maps and calibration counters)
+CONFIDENCE_HEADERS = ("catseg_hip_confidence.h",)
 
 BIG = 1 << 62
 
@@ -157,6 +159,11 @@ if set(_RENDER_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS) | set(_EXTENSION_
     raise RuntimeError("declared twice: "
                        f"{sorted(set(_RENDER_PROTOS) & (set(_PROTOS) | set(_INCLUDED_PROTOS) | set(_EXTENSION_PROTOS)))}")
 EXPORTED_RENDER = tuple(_RENDER_PROTOS)
+_CONFIDENCE_PROTOS = _read_included_headers(_STRUCTS, CONFIDENCE_HEADERS)
+_EARLIER = set(_PROTOS) | set(_INCLUDED_PROTOS) | set(_EXTENSION_PROTOS) | set(_RENDER_PROTOS)
+if set(_CONFIDENCE_PROTOS) & _EARLIER:
+    raise RuntimeError(f"declared twice: {sorted(set(_CONFIDENCE_PROTOS) & _EARLIER)}")
+EXPORTED_CONFIDENCE = tuple(_CONFIDENCE_PROTOS)
 # the struct classes under their header names without the prefix: RowMap, GemmArgs, RowsEpi, AdamWTensor, ...
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})
 F32, BF16, FP8 = (_ENUMS["CATSEG_" + n] for n in ("F32", "BF16", "FP8"))
@@ -183,7 +190,8 @@ def load() -> C.CDLL:
             f"libcatseg_hip.so not found at {LIB_PATH}: build it with "
             "`make -C cat-seg_amd/csrc` (or __graft_entry__.build()); the CAT-Seg HIP path has no fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS, **_EXTENSION_PROTOS, **_RENDER_PROTOS}.items():
+    for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS, **_EXTENSION_PROTOS, **_RENDER_PROTOS,
+                                      **_CONFIDENCE_PROTOS}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

@@ -21,6 +21,9 @@ REGIONS.OUTLINES by "regions_outlines", the regions' boundaries as polygon rings
 REGIONS.SIMPLIFY.ENABLED by "regions_outlines_simplified", those rings simplified arc by arc (ops.simplify_outlines).
 With MODEL.CATSEG_HIP.RENDER.ENABLED (OUTPUT "labels") every returned dict gains "sem_seg_render", the final label
 map as an RGB picture over its own input image (CATSeg.add_render; ops.render_labels).
+With MODEL.CATSEG_HIP.CONFIDENCE.ENABLED (OUTPUT "labels", plain and sliding branch) the maps come from
+ops.postprocess_topk: every dict gains "sem_seg_topk_labels", "sem_seg_topk_score" ((TOPK, H, W)) and "sem_seg_mass",
+and "sem_seg_labels" is rank 0 after the reject rule (MIN_SCORE, MIN_MARGIN, REJECT_LABEL).
 
 Everything between the input copy and the returned tensors runs in the HIP kernels of
 libcatseg_hip.so through `CatSegEngine`; there is no CPU or PyTorch-op fallback.
@@ -99,7 +102,9 @@ class CATSeg(nn.Module):
                  regions_connectivity: int = 8, regions_min_area: int = 0, regions_outlines: bool = False,
                  regions_simplify: bool = False, regions_simplify_tolerance: float = 1.0, render: bool = False,
                  render_alpha: float = 0.5, render_gray: bool = True, render_edge_px: int = 1, render_factor: int = 1,
-                 render_score_alpha: bool = False, render_palette: str = ""):
+                 render_score_alpha: bool = False, render_palette: str = "", confidence: bool = False,
+                 confidence_topk: int = 2, confidence_min_score: float = 0.0, confidence_min_margin: float = 0.0,
+                 confidence_reject_label: int = -1):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
@@ -140,6 +145,26 @@ class CATSeg(nn.Module):
                                 and 1 <= self.render_factor <= 64):
             raise ValueError("CATSeg: MODEL.CATSEG_HIP.RENDER needs ALPHA in [0, 1], EDGE_PX in 0 .. 8 and FACTOR in "
                              f"1 .. 64, got {render_alpha!r}, {render_edge_px!r}, {render_factor!r}")
+        # top-k maps, class mass and the reject rule (MODEL.CATSEG_HIP.CONFIDENCE; ops.postprocess_topk)
+        self.confidence = bool(confidence)
+        self.confidence_topk, self.confidence_reject_label = int(confidence_topk), int(confidence_reject_label)
+        self.confidence_min_score, self.confidence_min_margin = float(confidence_min_score), float(confidence_min_margin)
+        if self.confidence:
+            if output != "labels":
+                raise ValueError("CATSeg: MODEL.CATSEG_HIP.CONFIDENCE adds the top-k maps to the label map of "
+                                 f"MODEL.CATSEG_HIP.OUTPUT 'labels', not {output!r}")
+            if not 1 <= self.confidence_topk <= 4:
+                raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.CONFIDENCE.TOPK must be in 1 .. 4, got {confidence_topk!r}")
+            if self.confidence_reject_label < -1:
+                raise ValueError("CATSeg: MODEL.CATSEG_HIP.CONFIDENCE.REJECT_LABEL must be a label >= 0, or -1 for the "
+                                 f"number of test classes, got {confidence_reject_label!r}")
+            if tiled:
+                raise ValueError("CATSeg: MODEL.CATSEG_HIP.CONFIDENCE does not serve MODEL.CATSEG_HIP.TILED: the tiled "
+                                 "merge ranks averaged probabilities and keeps one class per pixel")
+            if tta_merge == "device":
+                raise ValueError("CATSeg: MODEL.CATSEG_HIP.CONFIDENCE does not serve MODEL.CATSEG_HIP.TTA_MERGE "
+                                 "'device': the merge of the views ranks averaged probabilities and keeps one class "
+                                 "per pixel")
         # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
         self.tiled = bool(tiled)
         self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
@@ -200,6 +225,7 @@ class CATSeg(nn.Module):
         tiled = (hip.get("TILED", None) if hip else None) or {}
         regions = (hip.get("REGIONS", None) if hip else None) or {}
         render = (hip.get("RENDER", None) if hip else None) or {}
+        confidence = (hip.get("CONFIDENCE", None) if hip else None) or {}
         return {
             "backbone": None,
             "sem_seg_head": build_sem_seg_head(cfg, None),
@@ -241,6 +267,11 @@ class CATSeg(nn.Module):
             "render_factor": int(render.get("FACTOR", 1)),
             "render_score_alpha": bool(render.get("SCORE_ALPHA", False)),
             "render_palette": str(render.get("PALETTE", "")),
+            "confidence": bool(confidence.get("ENABLED", False)),
+            "confidence_topk": int(confidence.get("TOPK", 2)),
+            "confidence_min_score": float(confidence.get("MIN_SCORE", 0.0)),
+            "confidence_min_margin": float(confidence.get("MIN_MARGIN", 0.0)),
+            "confidence_reject_label": int(confidence.get("REJECT_LABEL", -1)),
         }
 
     # ------------------------------------------------------------------ parameters
@@ -342,6 +373,10 @@ class CATSeg(nn.Module):
         tensors; each image's result (_label_result) holds views of them.  `images`: the input images of
         `logits`, which MODEL.CATSEG_HIP.RENDER draws over."""
         n, dev = logits.shape[0], logits.device
+        if self.confidence:
+            maps = ops.postprocess_topk(logits, self.confidence_topk, crop=crop, out_hw=hw,
+                                        reject=self.confidence_reject(logits.shape[1]))
+            return [self._confidence_result(maps, i, None if images is None else images[i]) for i in range(n)]
         labels = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.int32)
         score = torch.empty(n, hw[0], hw[1], device=dev, dtype=torch.float32)
         ops.postprocess_argmax(logits, labels, score, crop=crop)
@@ -352,14 +387,37 @@ class CATSeg(nn.Module):
         over `image`, its picture (add_render)."""
         return self.add_regions({"sem_seg_labels": labels, "sem_seg_score": score}, image)
 
+    def confidence_reject(self, n_classes: int):
+        """MODEL.CATSEG_HIP.CONFIDENCE's reject rule as ops.postprocess_topk takes it, (MIN_SCORE, MIN_MARGIN, label)
+        with REJECT_LABEL -1 resolved to `n_classes`; None while both thresholds are 0 (nothing is rejected and the
+        label map is rank 0 itself)."""
+        if not self.confidence or (self.confidence_min_score <= 0.0 and self.confidence_min_margin <= 0.0):
+            return None
+        label = self.confidence_reject_label if self.confidence_reject_label >= 0 else int(n_classes)
+        return self.confidence_min_score, self.confidence_min_margin, label
+
+    def _confidence_result(self, maps: dict, i: int, image=None) -> dict:
+        """Image i of ops.postprocess_topk's maps as one OUTPUT "labels" result: "sem_seg_labels" is rank 0 after
+        the reject rule, "sem_seg_score" rank 0's score, and the top-k maps and the mass ride along through
+        add_regions / add_render."""
+        labels = maps["labels"][i] if "labels" in maps else maps["topk_labels"][i, 0]
+        return self.add_regions({"sem_seg_labels": labels, "sem_seg_score": maps["topk_score"][i, 0],
+                                 "sem_seg_topk_labels": maps["topk_labels"][i],
+                                 "sem_seg_topk_score": maps["topk_score"][i], "sem_seg_mass": maps["mass"][i]}, image)
+
     def _palette(self, device) -> torch.Tensor:
         """The (P, 3) uint8 palette of MODEL.CATSEG_HIP.RENDER on `device`: RENDER.PALETTE's catalog colours, or
-        the colour map over the test classes; made once per class count."""
+        the colour map over the test classes; made once per class count.  With MODEL.CATSEG_HIP.CONFIDENCE rejecting
+        into a label beyond the test classes, black rows up to that label."""
         n = int(self.sem_seg_head.predictor.class_tokens("test").shape[0])
         key = (n, str(device))
         if key not in self._render_palettes:
             from .visualize import palette_for
-            self._render_palettes[key] = palette_for(self.render_palette or None, n, device=device)
+            palette = palette_for(self.render_palette or None, n, device=device)
+            reject = self.confidence_reject(n)
+            if reject is not None and reject[2] >= palette.shape[0]:
+                palette = torch.cat([palette, palette.new_zeros((reject[2] + 1 - palette.shape[0], 3))])
+            self._render_palettes[key] = palette
         return self._render_palettes[key]
 
     def add_render(self, result: dict, image) -> dict:
@@ -419,6 +477,10 @@ class CATSeg(nn.Module):
         if self.render:
             raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.RENDER cannot be traced by torch.compile: the "
                                "picture is drawn by a launch outside the registered operators; call it eagerly")
+        if self.confidence:
+            raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.CONFIDENCE cannot be traced by torch.compile: "
+                               "the traced forward returns the argmax map alone; call it eagerly (the operator "
+                               "catseg::postprocess_topk itself traces)")
         handle = self._op_handle
         n_classes, res = custom_ops.head_meta(handle)
         images = [x["image"] for x in batched_inputs]
@@ -665,6 +727,11 @@ class CATSeg(nn.Module):
             raw, sizes_dev, _ = self._batch(eng, [x["image"] for x in inputs])
             res = eng.SLIDE_OUT
             out_hw = [(int(x.get("height", res)), int(x.get("width", res))) for x in inputs]
+            if self.output == "labels" and self.confidence:
+                n_classes = int(self.sem_seg_head.predictor.class_tokens("test").shape[0])
+                return [self._confidence_result(maps, 0, x["image"]) for x, maps in
+                        zip(inputs, eng.forward_sliding(raw, sizes_dev, out_hw, labels=True,
+                                                        topk=(self.confidence_topk, self.confidence_reject(n_classes))))]
             if self.output == "labels":
                 return [self._label_result(lab, sc, x["image"])
                         for x, (lab, sc) in zip(inputs, eng.forward_sliding(raw, sizes_dev, out_hw, labels=True))]

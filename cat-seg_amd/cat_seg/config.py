@@ -247,4 +247,16 @@ def add_cat_seg_config(cfg):
     cfg.MODEL.CATSEG_HIP.RENDER.FACTOR = 1
     cfg.MODEL.CATSEG_HIP.RENDER.SCORE_ALPHA = False
     cfg.MODEL.CATSEG_HIP.RENDER.PALETTE = ""
+    # OUTPUT "labels" only (plain and sliding branch): the maps are made by catseg_postprocess_topk and every
+    # returned dict gains "sem_seg_topk_labels" / "sem_seg_topk_score" ((TOPK, H, W): the TOPK best classes of a
+    # pixel and their values, rank 0 first) and "sem_seg_mass" ((H, W): the sum of the class values).
+    # "sem_seg_labels" is rank 0 with REJECT_LABEL where its score is below MIN_SCORE or, TOPK >= 2, leads rank 1
+    # by less than MIN_MARGIN; with both 0.0 nothing is rejected.  REJECT_LABEL -1 = the number of test classes,
+    # the row the evaluators' confusion matrix accepts as a prediction.  TOPK 1 .. 4
+    cfg.MODEL.CATSEG_HIP.CONFIDENCE = C()
+    cfg.MODEL.CATSEG_HIP.CONFIDENCE.ENABLED = False
+    cfg.MODEL.CATSEG_HIP.CONFIDENCE.TOPK = 2
+    cfg.MODEL.CATSEG_HIP.CONFIDENCE.MIN_SCORE = 0.0
+    cfg.MODEL.CATSEG_HIP.CONFIDENCE.MIN_MARGIN = 0.0
+    cfg.MODEL.CATSEG_HIP.CONFIDENCE.REJECT_LABEL = -1
     return cfg

@@ -14,6 +14,8 @@ need the dispatcher); these are the registered surface for code that composes th
   catseg::postprocess      sigmoid + bilinear resize (catseg_postprocess; cat_seg_model.py:222-228)
   catseg::postprocess_argmax  the same fused with the argmax over the classes -> (labels, score)
                            (catseg_postprocess_argmax; + plain_train_net.py:107-116)
+  catseg::postprocess_topk the same keeping the k best classes and the class sum -> (topk_labels, topk_score,
+                           mass) (catseg_postprocess_topk)
   catseg::postprocess_tta, catseg::postprocess_tta_argmax  the merge of K test-time-augmentation views of
                            one image -> probabilities / (labels, score) (catseg_postprocess_tta;
                            test_time_augmentation.py:81-108)
@@ -141,6 +143,23 @@ def postprocess_argmax(logits: torch.Tensor, H: int, W: int, crop_h: int, crop_w
 def _(logits, H, W, crop_h, crop_w, sigmoid):
     return (logits.new_empty((logits.shape[0], H, W), dtype=torch.int32),
             logits.new_empty((logits.shape[0], H, W), dtype=torch.float32))
+
+
+@torch.library.custom_op("catseg::postprocess_topk", mutates_args=())
+def postprocess_topk(logits: torch.Tensor, k: int, H: int, W: int, crop_h: int, crop_w: int,
+                     sigmoid: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The k best classes of what catseg::postprocess (sigmoid) / the plain bilinear resize (not sigmoid)
+    computes, and the class-order sum: (B, T, h, w) fp32 -> topk_labels (B, k, H, W) int32, topk_score
+    (B, k, H, W) fp32, mass (B, H, W) fp32 (catseg_postprocess_topk)."""
+    out = ops.postprocess_topk(logits.contiguous(), k, crop=(crop_h, crop_w), sigmoid=sigmoid, out_hw=(H, W))
+    return out["topk_labels"], out["topk_score"], out["mass"]
+
+
+@postprocess_topk.register_fake
+def _(logits, k, H, W, crop_h, crop_w, sigmoid):
+    B = logits.shape[0]
+    return (logits.new_empty((B, k, H, W), dtype=torch.int32), logits.new_empty((B, k, H, W), dtype=torch.float32),
+            logits.new_empty((B, H, W), dtype=torch.float32))
 
 
 def _tta_views(logits, crop_h, crop_w, flip):

@@ -865,15 +865,21 @@ class CatSegEngine:
         ops.sliding_merge(logits, merged, kernel=k, stride=stride, out_res=res)
         return (merged, logits) if return_crops else merged
 
-    def forward_sliding(self, raw: torch.Tensor, sizes: torch.Tensor, out_hw, labels: bool = False) -> list:
+    def forward_sliding(self, raw: torch.Tensor, sizes: torch.Tensor, out_hw, labels: bool = False,
+                        topk=None) -> list:
         """Sliding-window probabilities resized to out_hw[n] = (height, width) per image
         (sem_seg_postprocess of the 640² merge, cat_seg_model.py:215-217).  labels=True: per image the
         (argmax map int32, its probability fp32) of that resize instead (catseg_postprocess_argmax without
-        the sigmoid, the 640 x 640 output included)."""
+        the sigmoid, the 640 x 640 output included).  labels=True with topk = (k, reject): per image the dict of
+        ops.postprocess_topk (batch of one, without the sigmoid, with the mass) instead of the pair."""
         merged = self.sliding_logits(raw, sizes)
         res = self.SLIDE_OUT
         outs = []
         for n, (H, W) in enumerate(out_hw):
+            if labels and topk is not None:
+                outs.append(ops.postprocess_topk(merged[n:n + 1], topk[0], crop=(res, res), sigmoid=False,
+                                                 reject=topk[1], out_hw=(H, W)))
+                continue
             if labels:
                 lab = torch.empty(1, H, W, device=self.device, dtype=torch.int32)
                 sc = torch.empty(1, H, W, device=self.device, dtype=_f32)

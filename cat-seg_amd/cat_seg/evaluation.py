@@ -28,6 +28,11 @@ eroded-boundary mIoU / pACC / mF1 per width; no counterpart in the reference): `
 counters on the device from the argmax map and the ground truth (`ops.boundary_confusion`:
 catseg_boundary_distance of both maps + catseg_boundary_confusion) and `evaluate()` forms
 `boundary_metrics` from the reduced counters.  Without it nothing changes.
+
+With `confidence={...}` they also report calibration (ECE, MCE, pACC@k, a reliability table and the coverage /
+selective-pACC curve; no counterpart in the reference): `process()` bins the counters on the device
+(`ops.confidence_bins`) from the top-k maps of a MODEL.CATSEG_HIP.CONFIDENCE "labels" output, or of a probability
+volume after one `ops.postprocess_topk`, and `evaluate()` forms `confidence_metrics`.  Without it nothing changes.
 """
 from __future__ import annotations
 
@@ -272,8 +277,65 @@ def boundary_metrics(conf, counters, class_names: Sequence[str], tags: Sequence[
     return res
 
 
+def confidence_spec(confidence) -> dict:
+    """The `confidence=` argument of the evaluators, checked and completed: {"bins": 1 .. 256 (15), "kind": "score"
+    (the confidence of a pixel is the score of its rank-0 class) | "normalized" (that score / the mass of the class
+    scores), "topk": 1 .. 4 (2), the ranks of pACC@k}."""
+    if not isinstance(confidence, dict) or set(confidence) - {"bins", "kind", "topk"}:
+        raise ValueError(f"confidence must be a dict with the keys bins, kind and topk, got {confidence!r}")
+    spec = {"bins": int(confidence.get("bins", 15)), "kind": confidence.get("kind", "score"),
+            "topk": int(confidence.get("topk", 2))}
+    if not 1 <= spec["bins"] <= 256:
+        raise ValueError(f"confidence: bins must lie in 1 .. 256, got {confidence.get('bins')!r}")
+    if spec["kind"] not in ("score", "normalized"):
+        raise ValueError(f"confidence: kind must be 'score' or 'normalized', got {spec['kind']!r}")
+    if not 1 <= spec["topk"] <= 4:
+        raise ValueError(f"confidence: topk must lie in 1 .. 4, got {confidence.get('topk')!r}")
+    return spec
+
+
+def confidence_metrics(counters, n_bins: int, K: int) -> dict:
+    """The calibration metrics from the reduced counters of catseg_confidence_bins (3 n_bins + K + 2 integers:
+    count, correct, conf_q24 per bin, hit per rank, valid, nan), every ratio in percent:
+      ECE = sum over the bins of n_b / N |acc_b - conf_b|, MCE = the largest |acc_b - conf_b| of a bin with pixels
+      (acc_b = correct_b / n_b, conf_b = the mean confidence conf_q24_b / 2^24 / n_b, N = sum n_b);
+      pACC@k for k = 1 .. K = hit[k - 1] / valid: the share of pixels whose ground truth is among ranks 0 .. k-1;
+      reliability = {"count", "accuracy", "confidence"}: per bin n_b, acc_b and conf_b (nan for an empty bin);
+      coverage, selective-pACC = per bin b, the share of the pixels in bins >= b and the accuracy among them: what
+      remains when everything below confidence b / n_bins is rejected (nan where nothing remains);
+      nan-confidence = the number of pixels with a NaN confidence (they enter nothing else)."""
+    c = np.asarray(counters, dtype=np.int64).reshape(-1)
+    if c.size != 3 * n_bins + K + 2:
+        raise ValueError(f"confidence_metrics: {c.size} counters do not match {n_bins} bins and K = {K}")
+    count, correct, q24 = (c[i * n_bins:(i + 1) * n_bins].astype(np.float64) for i in range(3))
+    hit, valid, nans = c[3 * n_bins:3 * n_bins + K].astype(np.float64), float(c[-2]), int(c[-1])
+    total = count.sum()
+    some = count > 0
+    safe = np.where(some, count, 1.0)
+    acc = np.where(some, correct / safe, np.nan)
+    conf = np.where(some, q24 / 16777216.0 / safe, np.nan)
+    gap = np.where(some, np.abs(correct / safe - q24 / 16777216.0 / safe), 0.0)
+    res = {"ECE": 100 * float((count * gap).sum() / total) if total else float("nan"),
+           "MCE": 100 * float(gap.max()) if total else float("nan")}
+    for k in range(K):
+        res[f"pACC@{k + 1}"] = 100 * hit[k] / valid if valid else float("nan")
+    kept = count[::-1].cumsum()[::-1]
+    kept_correct = correct[::-1].cumsum()[::-1]
+    res["reliability"] = {"count": count.astype(np.int64).tolist(), "accuracy": (100 * acc).tolist(),
+                          "confidence": (100 * conf).tolist()}
+    res["coverage"] = (100 * kept / total).tolist() if total else [float("nan")] * n_bins
+    res["selective-pACC"] = np.where(kept > 0, 100 * kept_correct / np.where(kept > 0, kept, 1.0), np.nan).tolist()
+    res["nan-confidence"] = nans
+    return res
+
+
 class SemSegEvaluator:
     """reset() / process(inputs, outputs) / evaluate() -> {"sem_seg": metrics}.
+
+    `confidence`: None, or a dict (`confidence_spec`) that turns the calibration metrics on: ECE, MCE, pACC@k, the
+    reliability table and the coverage / selective-pACC curve (`confidence_metrics`), their counters binned on the
+    device (ops.confidence_bins) from the top-k maps of a MODEL.CATSEG_HIP.CONFIDENCE "labels" output, or from
+    one identity-size ops.postprocess_topk of a "sem_seg" probability output, and added to the "sem_seg" dict.
 
     `boundary`: None, or up to 8 width specs (`boundary_specs`) that turn the boundary-aware metrics on:
     Boundary IoU, trimap and eroded-boundary mIoU / pACC / mF1 per width (`boundary_metrics`), their counters
@@ -288,11 +350,13 @@ class SemSegEvaluator:
 
     def __init__(self, dataset_name: Optional[str] = None, distributed: bool = True, output_dir=None, *,
                  class_names: Optional[Sequence[str]] = None, ignore_label: Optional[int] = None,
-                 gt_loader: Optional[Callable] = None, device=None, rle: str = "device", boundary=None):
+                 gt_loader: Optional[Callable] = None, device=None, rle: str = "device", boundary=None,
+                 confidence=None):
         if rle not in ("device", "host"):
             raise ValueError(f"SemSegEvaluator: rle must be 'device' or 'host', got {rle!r}")
         self._rle = rle
         self._boundary = boundary_specs(boundary) if boundary is not None else None
+        self._confidence = confidence_spec(confidence) if confidence is not None else None
         meta = _metadata(dataset_name)
         if class_names is None:
             class_names = meta.get("stuff_classes") if meta is not None else None
@@ -322,6 +386,24 @@ class SemSegEvaluator:
             n = self._num_classes
             self._bcounters = torch.zeros(len(self._boundary) * (n1 * n1 + 3 * n), dtype=torch.int64,
                                           device=self._device)
+        if self._confidence is not None:
+            self._ccounters = torch.zeros(3 * self._confidence["bins"] + self._confidence["topk"] + 2,
+                                          dtype=torch.int64, device=self._device)
+
+    def _confidence_update(self, topk_labels, topk_score, mass, gt):
+        """The calibration counters of one image from its top-k maps ((K, H, W), K >= topk) and, for the
+        normalised kind, its mass."""
+        K = self._confidence["topk"]
+        if topk_labels.dim() != 3 or topk_labels.shape[0] < K or tuple(topk_labels.shape[1:]) != tuple(gt.shape):
+            raise ValueError(f"confidence: top-k maps {tuple(topk_labels.shape)} do not hold {K} ranks of a "
+                             f"{tuple(gt.shape)} image")
+        conf = topk_score[0]
+        if self._confidence["kind"] == "normalized":
+            conf = conf / mass
+        ops.confidence_bins(topk_labels[:K].to(self._device, torch.int32).contiguous(),
+                            conf.to(self._device, torch.float32).contiguous(), gt, self._ccounters,
+                            num_classes=self._num_classes, ignore_label=self._ignore_label,
+                            clamp_pred=self.clamp_pred, n_bins=self._confidence["bins"])
 
     @property
     def boundary_tags(self) -> list:
@@ -354,6 +436,13 @@ class SemSegEvaluator:
         for inp, out in zip(inputs, outputs):
             if isinstance(out, dict) and "sem_seg_labels" in out:
                 self._process_labels(inp, out["sem_seg_labels"])
+                if self._confidence is not None:
+                    missing = [k for k in ("sem_seg_topk_labels", "sem_seg_topk_score", "sem_seg_mass") if k not in out]
+                    if missing:
+                        raise ValueError(f"SemSegEvaluator(confidence=...): the 'labels' output has no {missing}: "
+                                         "build the model with MODEL.CATSEG_HIP.CONFIDENCE.ENABLED")
+                    self._confidence_update(out["sem_seg_topk_labels"], out["sem_seg_topk_score"],
+                                            out["sem_seg_mass"], self._gt(inp))
                 continue
             probs = out["sem_seg"] if isinstance(out, dict) else out
             probs = probs.to(self._device, torch.float32).contiguous()
@@ -367,6 +456,11 @@ class SemSegEvaluator:
             labels = probs.argmax(dim=0).to(torch.int32) if device_rle or self._boundary is not None else None
             if self._boundary is not None:
                 self._boundary_update(labels, gt)
+            if self._confidence is not None:
+                # the top-k maps of the volume itself: one identity-size launch, no sigmoid
+                maps = ops.postprocess_topk(probs[None], self._confidence["topk"], sigmoid=False,
+                                            out_hw=tuple(probs.shape[1:]))
+                self._confidence_update(maps["topk_labels"][0], maps["topk_score"][0], maps["mass"][0], gt)
             if device_rle:
                 # the records are written only with an output_dir (the reference builds them for every
                 # image); only the label runs of the argmax map are brought to the host
@@ -455,6 +549,9 @@ class SemSegEvaluator:
         bcounters = None
         if self._boundary is not None:
             bcounters = (reduce_confusion(self._bcounters) if self._distributed else self._bcounters.cpu()).numpy()
+        ccounters = None
+        if self._confidence is not None:
+            ccounters = (reduce_confusion(self._ccounters) if self._distributed else self._ccounters.cpu()).numpy()
         preds = self.predictions() if self._output_dir else None
         if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
             return None
@@ -467,6 +564,8 @@ class SemSegEvaluator:
         res = self._metrics(conf)
         if bcounters is not None:
             res.update(boundary_metrics(conf, bcounters, self._class_names, [s[2] for s in self._boundary]))
+        if ccounters is not None:
+            res.update(confidence_metrics(ccounters, self._confidence["bins"], self._confidence["topk"]))
         if self._output_dir:
             torch.save(res, os.path.join(self._output_dir, "sem_seg_evaluation.pth"))
         return OrderedDict({"sem_seg": res})

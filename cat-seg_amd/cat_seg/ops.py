@@ -558,6 +558,55 @@ def postprocess_argmax(logits, labels, score=None, *, crop=None, sigmoid=True):
     return labels
 
 
+def postprocess_topk(logits, k, *, crop=None, sigmoid=True, mass=True, reject=None, out_hw):
+    """The k best classes of every pixel of the sigmoid'ed (sigmoid=True, as `postprocess`) or plain (as
+    `resize_bilinear`) fp32 planes [B][T][h][w] cropped to `crop` and resized to out_hw = (H, W)
+    (catseg_postprocess_topk; DESIGN.md section 4, "Confidence outputs"); the (B, T, H, W) volume is never
+    written.  1 <= k <= min(4, T).  Returns a dict of fresh tensors: "topk_labels" (B, k, H, W) int32 and
+    "topk_score" (B, k, H, W) fp32, rank 0 first (a NaN above every number, then the larger value, the lower
+    class among equals: torch.sort(descending=True, stable=True) cut at k; plane 0 is `postprocess_argmax`);
+    with mass=True "mass" (B, H, W) fp32, the class-order fp32 sum over all T classes; with reject =
+    (min_score, min_margin, reject_label) "labels" (B, H, W) int32, plane 0 with reject_label where
+    score_0 < min_score or (k >= 2 and) score_0 - score_1 < min_margin."""
+    B, T, h, w = logits.shape
+    H, W = (int(e) for e in out_hw)
+    k = int(k)
+    ch, cw = crop if crop is not None else (h, w)
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    dev = logits.device
+    out = {"topk_labels": torch.empty((B, k, H, W), dtype=torch.int32, device=dev),
+           "topk_score": torch.empty((B, k, H, W), dtype=torch.float32, device=dev)}
+    if mass:
+        out["mass"] = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    min_score, min_margin, reject_label = (0.0, 0.0, 0) if reject is None else reject
+    if reject is not None:
+        out["labels"] = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    # the crop read once; 2 k + mass + labels maps written
+    nbytes = 4 * B * (T * ch * cw + H * W * (2 * k + (1 if mass else 0) + (0 if reject is None else 1)))
+    with _rec("postprocess_topk", 0, nbytes):
+        call("catseg_postprocess_topk", logits.data_ptr(), B, T, h, w, ch, cw, 1 if sigmoid else 0, k,
+             out["topk_labels"].data_ptr(), out["topk_score"].data_ptr(), _p(out.get("mass")), _p(out.get("labels")),
+             float(min_score), float(min_margin), int(reject_label), H, W, _stream())
+    return out
+
+
+def confidence_bins(topk_labels, conf, gt, counters, *, num_classes, ignore_label=255, clamp_pred=-1, n_bins=15):
+    """counters += the calibration counters of one image (catseg_confidence_bins): topk_labels (K, H, W) int32,
+    conf (H, W) fp32 (the confidence of rank 0), gt (H, W) int32, counters (3 n_bins + K + 2,) int64 = count,
+    correct, conf_q24 (n_bins each), hit (K), valid, nan.  Returns counters."""
+    K, H, W = topk_labels.shape
+    n_bins = int(n_bins)
+    assert topk_labels.dtype == torch.int32 and topk_labels.is_contiguous()
+    assert conf.dtype == torch.float32 and conf.is_contiguous() and conf.shape == (H, W)
+    assert gt.dtype == torch.int32 and gt.is_contiguous() and gt.shape == (H, W)
+    assert conf.device == topk_labels.device and gt.device == topk_labels.device and counters.device == gt.device
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() == 3 * n_bins + K + 2
+    with _rec("confidence_bins", 0, 4 * H * W * (K + 2)):
+        call("catseg_confidence_bins", topk_labels.data_ptr(), K, conf.data_ptr(), gt.data_ptr(), H, W,
+             int(num_classes), int(ignore_label), int(clamp_pred), n_bins, counters.data_ptr(), _stream())
+    return counters
+
+
 def postprocess_tta(logits, views, *, probs=None, labels=None, score=None):
     """Merge of K test-time-augmentation views of one image (catseg_postprocess_tta): per view the
     sigmoid + crop + bilinear resize of `postprocess`, mirrored views flipped back, summed in view

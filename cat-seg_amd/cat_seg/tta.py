@@ -43,6 +43,10 @@ class SemanticSegmentorWithTTA(_tta.SemanticSegmentorWithTTA):
         if merge == "device" and bool(getattr(inner, "sliding_window", False)):
             raise ValueError("SemanticSegmentorWithTTA: MODEL.CATSEG_HIP.TTA_MERGE 'device' merges the views' logits "
                              "before the resize, which TEST.SLIDING_WINDOW has no single tensor of: use 'host'")
+        if merge == "device" and bool(getattr(inner, "confidence", False)):
+            raise ValueError("SemanticSegmentorWithTTA: MODEL.CATSEG_HIP.TTA_MERGE 'device' does not serve "
+                             "MODEL.CATSEG_HIP.CONFIDENCE: the merge of the views ranks averaged probabilities and "
+                             "keeps one class per pixel")
         super().__init__(cfg, model, tta_mapper=tta_mapper, batch_size=batch_size)
         self.tta_merge = merge
 

@@ -717,5 +717,7 @@ int catseg_region_outlines_write(const int32_t* ids, int64_t H, int64_t W, int64
 #include "catseg_hip_boundary.h"
 /* catseg_render_labels: a label map as an RGB picture (overlay, edges, error map, quicklook) */
 #include "catseg_hip_render.h"
+/* catseg_postprocess_topk, catseg_confidence_bins: top-k label maps with mass and reject, calibration counters */
+#include "catseg_hip_confidence.h"
 
 #endif /* CATSEG_HIP_H */
