@@ -28,6 +28,8 @@ EXTENSION_HEADERS = ("catseg_hip_boundary.h",)
 RENDER_HEADERS = ("catseg_hip_render.h",)
 # and a fourth (the confidence outputs: top-k label maps and calibration counters)
 CONFIDENCE_HEADERS = ("catseg_hip_confidence.h",)
+# and a fifth (the majority filter and the mode overviews of label maps)
+MODE_HEADERS = ("catseg_hip_mode.h",)
 
 BIG = 1 << 62
 
@@ -164,6 +166,10 @@ _EARLIER = set(_PROTOS) | set(_INCLUDED_PROTOS) | set(_EXTENSION_PROTOS) | set(_
 if set(_CONFIDENCE_PROTOS) & _EARLIER:
     raise RuntimeError(f"declared twice: {sorted(set(_CONFIDENCE_PROTOS) & _EARLIER)}")
 EXPORTED_CONFIDENCE = tuple(_CONFIDENCE_PROTOS)
+_MODE_PROTOS = _read_included_headers(_STRUCTS, MODE_HEADERS)
+if set(_MODE_PROTOS) & (_EARLIER | set(_CONFIDENCE_PROTOS)):
+    raise RuntimeError(f"declared twice: {sorted(set(_MODE_PROTOS) & (_EARLIER | set(_CONFIDENCE_PROTOS)))}")
+EXPORTED_MODE = tuple(_MODE_PROTOS)
 # the struct classes under their header names without the prefix: RowMap, GemmArgs, RowsEpi, AdamWTensor, ...
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})
 F32, BF16, FP8 = (_ENUMS["CATSEG_" + n] for n in ("F32", "BF16", "FP8"))
@@ -191,7 +197,7 @@ def load() -> C.CDLL:
             "`make -C cat-seg_amd/csrc` (or __graft_entry__.build()); the CAT-Seg HIP path has no fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_PROTOS, **_INCLUDED_PROTOS, **_EXTENSION_PROTOS, **_RENDER_PROTOS,
-                                      **_CONFIDENCE_PROTOS}.items():
+                                      **_CONFIDENCE_PROTOS, **_MODE_PROTOS}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

@@ -24,6 +24,9 @@ map as an RGB picture over its own input image (CATSeg.add_render; ops.render_la
 With MODEL.CATSEG_HIP.CONFIDENCE.ENABLED (OUTPUT "labels", plain and sliding branch) the maps come from
 ops.postprocess_topk: every dict gains "sem_seg_topk_labels", "sem_seg_topk_score" ((TOPK, H, W)) and "sem_seg_mass",
 and "sem_seg_labels" is rank 0 after the reject rule (MIN_SCORE, MIN_MARGIN, REJECT_LABEL).
+With MODEL.CATSEG_HIP.SMOOTH.ENABLED (OUTPUT "labels", every branch) "sem_seg_labels" is replaced by its majority
+filter (CATSeg.add_smooth; ops.mode_filter) before the sieve, the regions and the picture see it, and with
+MODEL.CATSEG_HIP.OVERVIEW.FACTORS every dict gains "sem_seg_overviews", {factor: ops.mode_overview of the final map}.
 
 Everything between the input copy and the returned tensors runs in the HIP kernels of
 libcatseg_hip.so through `CatSegEngine`; there is no CPU or PyTorch-op fallback.
@@ -104,7 +107,9 @@ class CATSeg(nn.Module):
                  render_alpha: float = 0.5, render_gray: bool = True, render_edge_px: int = 1, render_factor: int = 1,
                  render_score_alpha: bool = False, render_palette: str = "", confidence: bool = False,
                  confidence_topk: int = 2, confidence_min_score: float = 0.0, confidence_min_margin: float = 0.0,
-                 confidence_reject_label: int = -1):
+                 confidence_reject_label: int = -1, smooth: bool = False, smooth_size: int = 3,
+                 smooth_iterations: int = 1, smooth_rule: str = "plurality", smooth_weight: str = "count",
+                 smooth_reject: str = "keep", overview_factors: Tuple[int, ...] = (), overview_weight: str = "count"):
         super().__init__()
         if output not in ("probs", "labels"):
             raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OUTPUT must be 'probs' or 'labels', got {output!r}")
@@ -165,6 +170,39 @@ class CATSeg(nn.Module):
                 raise ValueError("CATSeg: MODEL.CATSEG_HIP.CONFIDENCE does not serve MODEL.CATSEG_HIP.TTA_MERGE "
                                  "'device': the merge of the views ranks averaged probabilities and keeps one class "
                                  "per pixel")
+        # majority filter of the returned label maps (MODEL.CATSEG_HIP.SMOOTH; ops.mode_filter)
+        self.smooth = bool(smooth)
+        self.smooth_size, self.smooth_iterations = int(smooth_size), int(smooth_iterations)
+        self.smooth_rule, self.smooth_weight, self.smooth_reject = str(smooth_rule), str(smooth_weight), str(smooth_reject)
+        if self.smooth and output != "labels":
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.SMOOTH filters the label map of "
+                             f"MODEL.CATSEG_HIP.OUTPUT 'labels', not {output!r}")
+        if self.smooth_size % 2 != 1 or not 3 <= self.smooth_size <= 15:
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.SMOOTH.SIZE must be odd, 3 .. 15, got {smooth_size!r}")
+        if not 1 <= self.smooth_iterations <= 8:
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.SMOOTH.ITERATIONS must be in 1 .. 8, got {smooth_iterations!r}")
+        if self.smooth_rule not in ("plurality", "half"):
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.SMOOTH.RULE must be 'plurality' or 'half', got {smooth_rule!r}")
+        if self.smooth_weight not in ("count", "score"):
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.SMOOTH.WEIGHT must be 'count' or 'score', got {smooth_weight!r}")
+        if self.smooth_reject not in ("keep", "fill"):
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.SMOOTH.REJECT must be 'keep' or 'fill', got {smooth_reject!r}")
+        # mode-resampled overviews of the final label map (MODEL.CATSEG_HIP.OVERVIEW; ops.mode_overview)
+        try:
+            self.overview_factors = tuple(int(f) for f in overview_factors)
+        except (TypeError, ValueError):
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.OVERVIEW.FACTORS must be a tuple of ints, got "
+                             f"{overview_factors!r}") from None
+        self.overview_weight = str(overview_weight)
+        if self.overview_factors and output != "labels":
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.OVERVIEW reduces the label map of "
+                             f"MODEL.CATSEG_HIP.OUTPUT 'labels', not {output!r}")
+        if (any(not 2 <= f <= 32 for f in self.overview_factors)
+                or len(set(self.overview_factors)) != len(self.overview_factors)):
+            raise ValueError("CATSeg: MODEL.CATSEG_HIP.OVERVIEW.FACTORS must be distinct ints in 2 .. 32, got "
+                             f"{overview_factors!r}")
+        if self.overview_weight not in ("count", "score"):
+            raise ValueError(f"CATSeg: MODEL.CATSEG_HIP.OVERVIEW.WEIGHT must be 'count' or 'score', got {overview_weight!r}")
         # tiled inference at native resolution (MODEL.CATSEG_HIP.TILED; cat_seg.tiling, engine.forward_tiled)
         self.tiled = bool(tiled)
         self.tiled_tile, self.tiled_stride, self.tiled_batch = int(tiled_tile), int(tiled_stride), int(tiled_batch)
@@ -226,6 +264,8 @@ class CATSeg(nn.Module):
         regions = (hip.get("REGIONS", None) if hip else None) or {}
         render = (hip.get("RENDER", None) if hip else None) or {}
         confidence = (hip.get("CONFIDENCE", None) if hip else None) or {}
+        smooth = (hip.get("SMOOTH", None) if hip else None) or {}
+        overview = (hip.get("OVERVIEW", None) if hip else None) or {}
         return {
             "backbone": None,
             "sem_seg_head": build_sem_seg_head(cfg, None),
@@ -272,6 +312,14 @@ class CATSeg(nn.Module):
             "confidence_min_score": float(confidence.get("MIN_SCORE", 0.0)),
             "confidence_min_margin": float(confidence.get("MIN_MARGIN", 0.0)),
             "confidence_reject_label": int(confidence.get("REJECT_LABEL", -1)),
+            "smooth": bool(smooth.get("ENABLED", False)),
+            "smooth_size": int(smooth.get("SIZE", 3)),
+            "smooth_iterations": int(smooth.get("ITERATIONS", 1)),
+            "smooth_rule": str(smooth.get("RULE", "plurality")),
+            "smooth_weight": str(smooth.get("WEIGHT", "count")),
+            "smooth_reject": str(smooth.get("REJECT", "keep")),
+            "overview_factors": tuple(overview.get("FACTORS", ())),
+            "overview_weight": str(overview.get("WEIGHT", "count")),
         }
 
     # ------------------------------------------------------------------ parameters
@@ -440,6 +488,40 @@ class CATSeg(nn.Module):
                                     score=result["sem_seg_score"] if self.render_score_alpha else None)
         return {**result, "sem_seg_render": picture}
 
+    def _reject_label(self):
+        """The label MODEL.CATSEG_HIP.CONFIDENCE's reject rule writes, or None while nothing is rejected."""
+        if self.confidence_reject(0) is None:
+            return None
+        if self.confidence_reject_label >= 0:
+            return self.confidence_reject_label
+        return self.confidence_reject(int(self.sem_seg_head.predictor.class_tokens("test").shape[0]))[2]
+
+    def add_smooth(self, result: dict) -> dict:
+        """MODEL.CATSEG_HIP.SMOOTH: "sem_seg_labels" replaced by its majority filter (ops.mode_filter with SIZE,
+        ITERATIONS and RULE; WEIGHT "score" votes with "sem_seg_score").  "sem_seg_score" and the top-k planes stay
+        as they are, as with the sieve.  The reject label of MODEL.CATSEG_HIP.CONFIDENCE casts no votes: REJECT
+        "keep" leaves rejected pixels rejected, "fill" lets their neighbourhood fill them.  ITERATIONS launches,
+        no host synchronisation.  A no-op with SMOOTH.ENABLED False."""
+        if not self.smooth:
+            return result
+        labels = ops.mode_filter(result["sem_seg_labels"], self.smooth_size, iterations=self.smooth_iterations,
+                                 rule=self.smooth_rule,
+                                 score=result["sem_seg_score"] if self.smooth_weight == "score" else None,
+                                 novote_label=self._reject_label(), fill=self.smooth_reject == "fill")
+        return {**result, "sem_seg_labels": labels}
+
+    def add_overviews(self, result: dict) -> dict:
+        """MODEL.CATSEG_HIP.OVERVIEW: "sem_seg_overviews" = {factor: ops.mode_overview of the final "sem_seg_labels"}
+        (after SMOOTH and the sieve), every factor from the full-resolution map; WEIGHT "score" votes with
+        "sem_seg_score"; the reject label of MODEL.CATSEG_HIP.CONFIDENCE casts no votes.  A no-op with FACTORS ()."""
+        if not self.overview_factors:
+            return result
+        score = result["sem_seg_score"] if self.overview_weight == "score" else None
+        novote = self._reject_label()
+        return {**result, "sem_seg_overviews": {f: ops.mode_overview(result["sem_seg_labels"], f, score=score,
+                                                                     novote_label=novote)
+                                                for f in self.overview_factors}}
+
     def add_regions(self, result: dict, image=None) -> dict:
         """MODEL.CATSEG_HIP.REGIONS: one image's {"sem_seg_labels", "sem_seg_score"} turned into objects, after
         the graph replay or the merge and outside any captured graph (the table's size depends on the data: one
@@ -451,9 +533,11 @@ class CATSeg(nn.Module):
         "regions_outlines_simplified" = ops.simplify_outlines of those rings under SIMPLIFY.TOLERANCE (two more
         4-byte reads: nodes, kept vertices); "regions_outlines" stays as it is.  A no-op with REGIONS.ENABLED
         False.  The junction every branch that returns labels passes: with `image` the result goes on through
-        add_render (MODEL.CATSEG_HIP.RENDER), drawn from the final map."""
+        add_render (MODEL.CATSEG_HIP.RENDER), drawn from the final map.  MODEL.CATSEG_HIP.SMOOTH filters the map
+        first (add_smooth), and MODEL.CATSEG_HIP.OVERVIEW reduces the final one (add_overviews)."""
+        result = self.add_smooth(result)
         if not self.regions:
-            return self.add_render(result, image)
+            return self.add_render(self.add_overviews(result), image)
         labels, conn = result["sem_seg_labels"], self.regions_connectivity
         if self.regions_min_area > 1:
             labels = ops.sieve_labels(labels, self.regions_min_area, connectivity=conn)
@@ -465,7 +549,7 @@ class CATSeg(nn.Module):
             if self.regions_simplify:
                 out["regions_outlines_simplified"] = ops.simplify_outlines(ids, out["regions_outlines"],
                                                                            self.regions_simplify_tolerance)
-        return self.add_render(out, image)
+        return self.add_render(self.add_overviews(out), image)
 
     def _forward_traced(self, batched_inputs: List[dict]):
         """The eval forward as dynamo traces it (torch.compile): the canvas staging in torch ops, the
@@ -474,6 +558,10 @@ class CATSeg(nn.Module):
         if self.regions:
             raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.REGIONS cannot be traced by torch.compile: the "
                                "region table's size depends on the data; call it eagerly")
+        if self.smooth or self.overview_factors:
+            raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.SMOOTH or MODEL.CATSEG_HIP.OVERVIEW cannot be "
+                               "traced by torch.compile: the filter and the overviews are launches outside the "
+                               "registered operators; call it eagerly")
         if self.render:
             raise RuntimeError("CATSeg.forward with MODEL.CATSEG_HIP.RENDER cannot be traced by torch.compile: the "
                                "picture is drawn by a launch outside the registered operators; call it eagerly")

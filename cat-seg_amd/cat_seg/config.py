@@ -259,4 +259,24 @@ def add_cat_seg_config(cfg):
     cfg.MODEL.CATSEG_HIP.CONFIDENCE.MIN_SCORE = 0.0
     cfg.MODEL.CATSEG_HIP.CONFIDENCE.MIN_MARGIN = 0.0
     cfg.MODEL.CATSEG_HIP.CONFIDENCE.REJECT_LABEL = -1
+    # OUTPUT "labels" only, every branch: "sem_seg_labels" is replaced by its majority filter (CATSeg.add_smooth,
+    # ops.mode_filter) before the sieve, the regions, the picture and the evaluators see it: every pixel takes the
+    # label with the most votes in its SIZE x SIZE window (odd, 3 .. 15, clipped to the map), ties to its own label,
+    # then to the smallest; ITERATIONS 1 .. 8 passes.  RULE "plurality" | "half" (write the winner only where it
+    # holds more than half of the window's votes).  WEIGHT "count" (one vote per pixel) | "score" (the pixel votes
+    # with "sem_seg_score" in Q16).  The reject label of CONFIDENCE casts no votes; REJECT "keep" leaves rejected
+    # pixels rejected, "fill" gives them their window's winner
+    cfg.MODEL.CATSEG_HIP.SMOOTH = C()
+    cfg.MODEL.CATSEG_HIP.SMOOTH.ENABLED = False
+    cfg.MODEL.CATSEG_HIP.SMOOTH.SIZE = 3
+    cfg.MODEL.CATSEG_HIP.SMOOTH.ITERATIONS = 1
+    cfg.MODEL.CATSEG_HIP.SMOOTH.RULE = "plurality"
+    cfg.MODEL.CATSEG_HIP.SMOOTH.WEIGHT = "count"
+    cfg.MODEL.CATSEG_HIP.SMOOTH.REJECT = "keep"
+    # OUTPUT "labels" only: every returned dict gains "sem_seg_overviews", {factor: ops.mode_overview of the final
+    # label map}: the map reduced by each factor (distinct ints in 2 .. 32), a cell taking its most frequent label
+    # (gdal's -r mode), with the winner's votes, the cell's total and their share.  WEIGHT as for SMOOTH
+    cfg.MODEL.CATSEG_HIP.OVERVIEW = C()
+    cfg.MODEL.CATSEG_HIP.OVERVIEW.FACTORS = ()
+    cfg.MODEL.CATSEG_HIP.OVERVIEW.WEIGHT = "count"
     return cfg

@@ -1105,6 +1105,91 @@ def render_labels(labels, palette, *, image=None, gray=True, alpha=0.5, score=No
     return out
 
 
+def _mode_votes_args(labels, score, novote_label, what):
+    """(H, W, ld, ld_score, has_novote, novote_label) of a label map and its optional vote arguments."""
+    H, W, ld = _label_map_args(labels, what)
+    if H > 16384 or W > 16384:
+        raise ValueError(f"{what}: H and W must lie in 1 .. 16384, got {H} x {W}")
+    ld_score = 0
+    if score is not None:
+        if not torch.is_tensor(score) or score.device != labels.device:
+            raise ValueError(f"{what}: score must be a tensor on the labels' device")
+        if score.dtype != torch.float32 or tuple(score.shape) != (H, W):
+            raise ValueError(f"{what}: score must be an ({H}, {W}) float32 tensor, got {score.dtype} "
+                             f"{tuple(score.shape)}")
+        if W > 1 and score.stride(1) != 1:
+            raise ValueError(f"{what}: the rows of score must be contiguous (stride {score.stride(1)})")
+        ld_score = score.stride(0) if H > 1 else W
+        if ld_score < W:
+            raise ValueError(f"{what}: row stride {ld_score} of score < W = {W}")
+    if novote_label is not None and (not isinstance(novote_label, int) or isinstance(novote_label, bool)
+                                     or not -2 ** 31 <= novote_label < 2 ** 31):
+        raise ValueError(f"{what}: novote_label must be None or an int32 value, got {novote_label!r}")
+    return H, W, ld, ld_score, int(novote_label is not None), 0 if novote_label is None else novote_label
+
+
+def mode_filter(labels, size=3, *, iterations=1, rule="plurality", score=None, novote_label=None, fill=False,
+                out=None):
+    """The majority (mode) filter of a label map on the device (catseg_mode_filter; DESIGN.md section 4, "Mode filter
+    and overviews"): every pixel takes the label with the greatest vote sum in its size x size window, clipped to the
+    map.  Among equal sums its own label wins if it is one of them, otherwise the smallest label value; a pixel whose
+    window holds no vote keeps its value.  Integer arithmetic, bit-exact against tests/mode_ref.py.
+      labels        2-D int32 CUDA map, rows may be strided; any int32 value is a label
+      size          odd, 3 .. 15; iterations 1 .. 8 applies the filter repeatedly (the score stays the same)
+      rule          "plurality": the winner is written; "half": only where it holds more than half of the window's
+                    votes, otherwise the pixel keeps its value
+      score         (H, W) float32, rows may be strided: a pixel casts clamp(rint(score * 65536), 0, 65536) votes
+                    (0 for a NaN) instead of 1
+      novote_label  pixels of this label cast no votes and keep their value; with fill=True they take their
+                    window's winner like any other pixel
+      out           (H, W) int32, rows may be strided, must not overlap labels (fresh when None)
+    Returns out.  One launch per iteration between two buffers, no workspace, no host synchronisation."""
+    what = "mode_filter"
+    H, W, ld, ld_score, has_novote, novote = _mode_votes_args(labels, score, novote_label, what)
+    if not isinstance(size, int) or isinstance(size, bool) or size % 2 != 1 or not 3 <= size <= 15:
+        raise ValueError(f"{what}: size must be an odd int in 3 .. 15, got {size!r}")
+    if not isinstance(iterations, int) or isinstance(iterations, bool) or not 1 <= iterations <= 8:
+        raise ValueError(f"{what}: iterations must be an int in 1 .. 8, got {iterations!r}")
+    if rule not in ("plurality", "half"):
+        raise ValueError(f"{what}: rule must be 'plurality' or 'half', got {rule!r}")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=labels.device)
+    if (not torch.is_tensor(out) or out.device != labels.device
+            or _label_map_args(out, f"{what} (out)")[:2] != (H, W)):
+        raise ValueError(f"{what}: out must be an ({H}, {W}) int32 tensor on the labels' device")
+    ld_out = out.stride(0) if H > 1 else W
+    # iteration i writes out when the iterations left after it are even, so that the last one does
+    other = torch.empty((H, W), dtype=torch.int32, device=labels.device) if iterations > 1 else None
+    src, ld_src = labels, ld
+    for i in range(iterations):
+        dst, ld_dst = (out, ld_out) if (iterations - 1 - i) % 2 == 0 else (other, W)
+        with _rec("mode_filter", 0, H * W * (8 + (4 if score is not None else 0))):
+            call("catseg_mode_filter", src.data_ptr(), H, W, ld_src, size, int(rule == "half"), _p(score), ld_score,
+                 has_novote, novote, int(bool(fill)), dst.data_ptr(), ld_dst, _stream())
+        src, ld_src = dst, ld_dst
+    return out
+
+
+def mode_overview(labels, factor, *, score=None, novote_label=None):
+    """A label map reduced by an integer factor on the device (catseg_mode_overview; DESIGN.md section 4, "Mode filter
+    and overviews"; gdal's -r mode): output (Y, X) of (ceil(H / factor), ceil(W / factor)) takes the label with the
+    greatest vote sum of input rows Y f .. min(H, Y f + f) - 1 and the columns likewise, ties to the smallest label
+    value; a cell without votes gets novote_label (without one: its smallest label value).  labels, score and
+    novote_label as for `mode_filter`; factor 2 .. 32.  Returns {"labels", "votes" (the winner's vote sum), "total"
+    (the cell's): int32; "share": float32 votes / total formed in fp64, NaN where total is 0}.  One launch, no
+    workspace, no host synchronisation."""
+    what = "mode_overview"
+    H, W, ld, ld_score, has_novote, novote = _mode_votes_args(labels, score, novote_label, what)
+    if not isinstance(factor, int) or isinstance(factor, bool) or not 2 <= factor <= 32:
+        raise ValueError(f"{what}: factor must be an int in 2 .. 32, got {factor!r}")
+    Ho, Wo = -(-H // factor), -(-W // factor)
+    out = torch.empty((3, Ho, Wo), dtype=torch.int32, device=labels.device)
+    with _rec("mode_overview", 0, H * W * (4 + (4 if score is not None else 0)) + 12 * Ho * Wo):
+        call("catseg_mode_overview", labels.data_ptr(), H, W, ld, factor, _p(score), ld_score, has_novote, novote,
+             out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream())
+    return {"labels": out[0], "votes": out[1], "total": out[2], "share": (out[1].double() / out[2].double()).float()}
+
+
 def label_runs_count(labels, *, clamp_pred=-1):
     """Count + scan half of `label_runs` (catseg_label_runs_count): returns the int32 workspace tensor, whose
     element 0 is the number of runs R (still on the device) and whose rest holds the write offsets."""

@@ -719,5 +719,7 @@ int catseg_region_outlines_write(const int32_t* ids, int64_t H, int64_t W, int64
 #include "catseg_hip_render.h"
 /* catseg_postprocess_topk, catseg_confidence_bins: top-k label maps with mass and reject, calibration counters */
 #include "catseg_hip_confidence.h"
+/* catseg_mode_filter, catseg_mode_overview: majority filter and mode-resampled overviews of label maps */
+#include "catseg_hip_mode.h"
 
 #endif /* CATSEG_HIP_H */
